@@ -1,6 +1,14 @@
 """Benchmark: NMPC solves/s of the MPC::Solve hot path on MI355X.
 
-    python bench.py [--gpus N --steps K --warmup W --batch B --horizon N]
+    python bench.py [--gpus N --steps K --warmup W --batch B --horizon N] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the result line (the roofline
+figures come from the HIP events of those same steps).  --full adds what takes runs of its
+own: cpu_baseline and latency_b1 (below).  --dump-outputs DIR writes what the last timed
+step computed as DIR/<name>.npy (float64): u0, traj, status, iters (--mode track: cmd, traj,
+status); at --gpus N > 1 the arrays gathered to rank 0.  Above 64 MB in all, the same seeded
+sample of rows of every array, their indices in rows.npy.  The inputs depend on the arguments
+alone, so two builds can be compared output for output.
 
 With --gpus N > 1 and no torch.distributed environment (RANK/WORLD_SIZE unset), the
 process launches N ranks itself -- `python -m torch.distributed.run --nproc-per-node N
@@ -29,7 +37,7 @@ summary of this exact configuration (profiles/r6/pmc_<model>_<mode>_<dtype>_B<B>
 or null.  The line also carries hbm = algorithmic bytes per launch (B x 8 x (6 + 4 + 2 +
 3N) = B x 576 B at N = 20) / kernel time against 8 TB/s, and valu_fp64 = PMC-counted
 FP64 lane-FLOPs (redundant lanes included) / kernel time.
-cpu_baseline: the oracle (the Ipopt restatement, "port") on a bounded sample of the
+cpu_baseline (--full): the oracle (the Ipopt restatement, "port") on a bounded sample of the
 same problems, rank 0, N = 1 only: its KKT systems in stage order factored within their
 band (the structured linear algebra, as Ipopt's sparse solver would) as the value, the
 checker's dense factorisation as a second figure.
@@ -70,7 +78,12 @@ def parse():
     ap.add_argument("--batch", type=int, default=65536, help="problems per GPU")
     ap.add_argument("--horizon", type=int, default=20)
     ap.add_argument("--gather-traj", action="store_true", help="also gather the 3N trajectories")
-    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="CPU baseline time budget (0 = skip)")
+    ap.add_argument("--full", action="store_true",
+                    help="also the figures that take runs of their own: cpu_baseline and latency_b1")
+    ap.add_argument("--cpu-seconds", type=float, default=12.0,
+                    help="with --full: CPU baseline time budget (0 = skip)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the arrays of the last timed step as DIR/<name>.npy (float64)")
     ap.add_argument("--profile-name", default=None, help="PMC summary to read traffic from")
     ap.add_argument("--strategy", default="auto", choices=["auto", "wave"],
                     help="kernel strategy: one problem per wavefront (the only one)")
@@ -184,6 +197,29 @@ def latency_b1(P, st, cf, solver, dev, reps=50):
     return {"gpu_device_ms": float(np.median(dev_ms)), "gpu_host_buffers_ms": float(np.median(host_ms)),
             "cpu_oracle_ms": float(np.median(cpu_ms)),
             "sample": f"problem 0 of the batch, B = 1, median of {reps} (GPU) / {min(reps, 20)} (CPU, 1 thread)"}
+
+
+DUMP_BUDGET = 64 * 1000 * 1000  # bytes, all files of --dump-outputs together
+
+
+def dump_outputs(path, tensors):
+    """--dump-outputs: the torch tensors of the last timed step (same number of rows each) as
+    path/<name>.npy in float64.  Above DUMP_BUDGET in all, a fixed seeded sample of rows (the
+    same rows of every array, ascending) and their indices as rows.npy."""
+    import torch
+
+    os.makedirs(path, exist_ok=True)
+    rows = len(next(iter(tensors.values())))
+    per_row = 8 * (1 + sum(t.numel() // max(rows, 1) for t in tensors.values()))  # (+ the row index)
+    keep = max(1, (DUMP_BUDGET - 128 * (len(tensors) + 1)) // per_row)  # (128: a .npy header)
+    idx = None
+    if keep < rows:
+        idx = np.sort(np.random.default_rng(20).choice(rows, size=keep, replace=False))
+        np.save(os.path.join(path, "rows.npy"), idx.astype(np.float64))
+    for name, t in tensors.items():
+        if idx is not None:
+            t = t[torch.from_numpy(idx).to(t.device)]
+        np.save(os.path.join(path, f"{name}.npy"), t.detach().cpu().numpy().astype(np.float64))
 
 
 def pmc_name(a) -> str:
@@ -307,7 +343,7 @@ def main():
         tcf = torch.empty((count, 4), dtype=torch.float64, device=dev)
         solver.preprocess_device(tpose, tvel, tplan, tst, tcf)
         torch.cuda.synchronize()
-        st, cf = (tst.cpu().numpy(), tcf.cpu().numpy()) if rank == 0 else (None, None)
+        st, cf = (tst.cpu().numpy(), tcf.cpu().numpy()) if rank == 0 and a.full else (None, None)
     else:
         st, cf = infinity.make_problems(np.arange(start, start + count))
         tst = torch.from_numpy(st).to(dev)
@@ -345,14 +381,13 @@ def main():
         if world > 1:
             g_u0 = D.gather_rows(cmd if a.mode == "track" else u0, total)
             g_st = D.gather_rows(status, total)
-            if a.gather_traj:
-                D.gather_rows(traj.view(count, -1), total)
+            g_traj = D.gather_rows(traj.view(count, -1), total) if a.gather_traj else None
             if timed:  # (the collectives are stream-ordered before this event)
                 e2 = torch.cuda.Event(enable_timing=True)
                 e2.record(stream)
                 g_ms.append((e1, e2))
-            return g_u0, g_st
-        return u0, status
+            return g_u0, g_st, g_traj
+        return cmd if a.mode == "track" else u0, status, traj
 
     for _ in range(a.warmup):
         step(False)
@@ -360,12 +395,20 @@ def main():
         dist.barrier()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
+    last = None
     for _ in range(a.steps):
-        step(True)
+        last = step(True)
     if world > 1:
         dist.barrier()
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
+    if a.dump_outputs and rank == 0 and last is not None:
+        out = {"cmd" if a.mode == "track" else "u0": last[0], "status": last[1]}
+        if last[2] is not None:
+            out["traj"] = last[2].view(len(last[2]), 3, N)
+        if world == 1 and a.mode == "solve":
+            out["iters"] = iters
+        dump_outputs(a.dump_outputs, out)
     kern = float(np.mean([e0.elapsed_time(e1) for e0, e1 in k_ms])) if k_ms else float("nan")
     gath = float(np.mean([e1.elapsed_time(e2) for e1, e2 in g_ms])) if g_ms else 0.0
     per_rank = None
@@ -456,7 +499,7 @@ def main():
                        "sample": "all problems of the last timed step, all ranks"},
             "timing": {"kernel_ms": kern, "gather_ms": gath, "per_rank": per_rank},
         }
-        if world == 1 and a.cpu_seconds > 0:
+        if a.full and world == 1 and a.cpu_seconds > 0:
             line["cpu_baseline"] = cpu_baseline(P, st, cf, a.cpu_seconds)
             line["latency_b1"] = latency_b1(P, st, cf, solver, dev)
         else:

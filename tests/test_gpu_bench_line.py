@@ -1,4 +1,4 @@
-"""The bench line's contract on the GPU: `python bench.py` (a short run) prints one JSON line
+"""The bench line's contract on the GPU: `python bench.py --full` (a short run) prints one JSON line
 with BASELINE.json's metric and the fields the driver and the judge read -- value, unit,
 n_gpus, steps, warmup, ms_per_step, higher_is_better, scaling, vs_baseline, dtype, data,
 config.workload, and the roofline and cpu_baseline objects (ROUND contract, item ④)."""
@@ -19,7 +19,7 @@ pytestmark = pytest.mark.gpu
 def test_bench_line_contract():
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")}
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1",
-                        "--cpu-seconds", "1"], capture_output=True, text=True, env=env, timeout=600)
+                        "--full", "--cpu-seconds", "1"], capture_output=True, text=True, env=env, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, r.stdout[-3000:]

@@ -18,7 +18,7 @@ smoke)
   timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1; rc=$?
   echo "smoke rc=$rc"; tail -1 $O/smoke.log; [ $rc -eq 0 ] || exit 1 ;;
 bench)
-  timeout -k 10 300 python bench.py > $O/bench.log 2>&1; rc=$?
+  timeout -k 10 300 python bench.py --full > $O/bench.log 2>&1; rc=$?
   echo "bench rc=$rc"; tail -1 $O/bench.log | cut -c1-300; [ $rc -eq 0 ] || exit 1 ;;
 cfg)
   for c in ${CFGS:-n20 b4096 lat n40 n40f32 n40f32r n20f32 bic25 track}; do
@@ -27,7 +27,7 @@ cfg)
       track) a="--mode track";; n100) a="--batch 4096 --horizon 100";; n64) a="--horizon 64";; bic40) a="--model bicycle --horizon 40";;
       b1024) a="--batch 1024";; lat) a="--batch 4096 --cpu-seconds 1";; n40f32off) a="--horizon 40 --dtype fp32 --restoration off";; esac
     timeout -k 10 300 python bench.py --steps ${CSTEPS:-10} --warmup 2 --cpu-seconds 0 $a > $O/cfg_$c.log 2>&1; rc=$?
-    [ "$c" = lat ] && { timeout -k 10 300 python bench.py --steps 5 --warmup 1 $a > $O/cfg_$c.log 2>&1; rc=$?; }
+    [ "$c" = lat ] && { timeout -k 10 300 python bench.py --full --steps 5 --warmup 1 $a > $O/cfg_$c.log 2>&1; rc=$?; }
     echo "$c rc=$rc"; [ $rc -eq 0 ] || exit 1
     tail -1 $O/cfg_$c.log > $O/cfg_$c.json
     python3 -c "import json; d=json.load(open('$O/cfg_$c.json')); print('  ', round(d['value']), round(d['roofline']['kernel_ms'],3), d['roofline']['kernel'], d['solver']['iters_mean'], d['solver']['status_counts'], d['solver']['restoration'], d['solver'].get('fp64_phase'), d.get('latency_b1'))"

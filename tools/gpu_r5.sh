@@ -16,7 +16,7 @@ smoke)
   timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1; rc=$?
   echo "smoke rc=$rc"; tail -1 $O/smoke.log; [ $rc -eq 0 ] || exit 1 ;;
 bench)
-  timeout -k 10 300 python bench.py > $O/bench.log 2>&1; rc=$?
+  timeout -k 10 300 python bench.py --full > $O/bench.log 2>&1; rc=$?
   echo "bench rc=$rc"; tail -1 $O/bench.log | cut -c1-300; [ $rc -eq 0 ] || exit 1 ;;
 cfg)
   TAG=$T STEPS=cfg bash tools/gpu_r4.sh || exit 1 ;;
