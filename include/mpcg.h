@@ -79,7 +79,8 @@ typedef struct mpcg_params {
     int32_t filter_cap;       /* filter entries held in LDS per problem (64); 448 more are kept in
                                  the HBM workspace, so the oldest entry is dropped only beyond
                                  filter_cap + 448 non-dominated entries (counted in diag[:, 1];
-                                 Ipopt's filter is unbounded) */
+                                 Ipopt's filter is unbounded).  Results are independent of
+                                 filter_cap while fewer than filter_cap + 448 entries are held */
     double bound_relax_factor;/* 1e-8 */
     double mu_init;           /* 0.1 */
     double wheelbase;         /* model 1 only: Lf [m] */
@@ -105,7 +106,8 @@ typedef struct mpcg_params {
     double tiny_step_y_tol;            /* 1e-2 */
     double dual_inf_tol;               /* 1 (unscaled dual infeasibility at termination) */
     double constr_viol_tol;            /* 1e-4 (unscaled constraint violation; caps the bound relaxation) */
-    double compl_inf_tol;              /* 1e-4 (unscaled complementarity; mu_min = min(tol, this) / 11) */
+    double compl_inf_tol;              /* 1e-4 (unscaled complementarity; mu_min = min(tol, this x objective scaling) / 11;
+                                          precision 1: min(tol, this) / 11) */
     int32_t acceptable_iter;           /* 15 (0: no acceptable termination) */
     int32_t max_soc;                   /* 4 (0: no second-order corrections) */
     int32_t watchdog_shortened_iter_trigger; /* 10 (0: no watchdog) */

@@ -3734,7 +3734,13 @@ struct WideSolver {
         s = wv.uni(s);
         if (s) return s;
         const T kappa_eps = 10, kappa_mu = (T)0.2, theta_mu = (T)1.5;
-        const T mu_min = (T)(fmin(P.tol, P.compl_inf_tol) / 11.0);  // min(tol, compl_inf_tol) / (kappa_eps + 1)
+        // min(tol, compl_inf_tol posed to the scaled problem) / (kappa_eps + 1)
+        // (MonotoneMuUpdate: apply_obj_scaling(compl_inf_tol))
+        // (= min(tol, c) / 11 exactly; the division only where the scaled compl_inf_tol is the minimum)
+        // (the fp32 solver keeps the unscaled compl_inf_tol: its options, solver.py FP32_OPTIONS, hold
+        // the floor above float resolution, and the fp64 phase finishes its rows)
+        const double cit_s = sizeof(T) == 8 ? (double)P.compl_inf_tol * (double)sf : (double)P.compl_inf_tol;
+        const T mu_min = wv.uni(cit_s < (double)P.tol) ? (T)(cit_s / 11.0) : (T)(P.tol / 11.0);
         int tf = tiny_flag;
         tiny_flag = 0;
         bool done = false;
@@ -4210,7 +4216,7 @@ struct WideSolver {
     // objective depends on mu), continued in k_rmu
     MPCG_HD int mu_loop() {
         const T kappa_eps = 10, kappa_mu = (T)0.2, theta_mu = (T)1.5;
-        const T mu_min = (T)(fmin(P.tol, P.compl_inf_tol) / 11.0);
+        const T mu_min = (T)(fmin(P.tol, P.compl_inf_tol) / 11.0);  // (the restoration problem's objective scaling is 1)
         for (;;) {
             if (!wv.uni((mu_Emu <= kappa_eps * mu || mu_tf) && !mu_done)) break;
             const T mnew = wv.uni_d(tmax(tmin(kappa_mu * mu, (T)pow((double)mu, (double)theta_mu)), mu_min));

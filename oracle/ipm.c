@@ -16,7 +16,7 @@
  * IpRestoIterateInitializer.cpp).  Defaults (3.12):
  *
  *   mu_init 0.1, barrier_tol_factor 10, mu_linear_decrease_factor 0.2,
- *   mu_superlinear_decrease_power 1.5, mu_min = min(tol, compl_inf_tol)/(kappa_eps + 1),
+ *   mu_superlinear_decrease_power 1.5, mu_min = min(tol, obj_scale compl_inf_tol)/(kappa_eps + 1),
  *   tau_min 0.99, bound_push = bound_frac = 0.01, bound_mult_init_val 1,
  *   constr_mult_init_max 1000 (least-squares y0), kappa_sigma 1e10, kappa_d 1e-5,
  *   gamma_theta 1e-5, gamma_phi 1e-8, delta 1, alpha_min_frac 0.05, s_theta 1.1,
@@ -1181,7 +1181,9 @@ static int resto_convergence(ipm* S) {
 static int ipm_iterate(ipm* S) {
     const ora_ipm_opts* o = S->o;
     const double kappa_eps = 10.0, kappa_mu = 0.2, theta_mu = 1.5;
-    const double mu_min = fmin(o->tol, o->compl_inf_tol) / (kappa_eps + 1.0);
+    /* MonotoneMuUpdate: compl_inf_tol is first posed to the scaled problem (apply_obj_scaling;
+     * the restoration problem's objective scaling is 1) */
+    const double mu_min = fmin(o->tol, o->compl_inf_tol * S->P->obj_scale) / (kappa_eps + 1.0);
     for (;;) {
         eval_current(S);
         {

@@ -28,6 +28,16 @@ All solves use the reference's options (oracle.pyoracle.ref_opts: Ipopt 3.12 def
 max_cpu_time 0.5 s as its iteration budget).
 
     python tests/golden/make_goldens.py [set ...]     (default: all sets)
+
+  option_cases.json  the option matrix of tests/test_option_matrix.py and tests/test_gpu_options.py:
+                     per case the option or parameter overrides and the infinity-set rows it runs
+                     on (names, numbers and indices only), chosen by a scan with the oracle --
+                     rows on which the case acts and on which the oracle's status and iteration
+                     count do not depend on its linear algebra; the same per kernel instance
+                     shape, on the restoration sets, and the fp32 solver's rows.  Not part of "all sets" (about ten
+                     minutes on 8 cores):
+
+    python tests/golden/make_goldens.py option_cases
 """
 from __future__ import annotations
 
@@ -205,8 +215,245 @@ def hs071():
                    "zu": [0.0, 0.0, 0.0, 0.0], "rel_tol": 1e-6, "abs_tol": 1e-6}, f, indent=1)
 
 
+# ---------------------------------------------------------------- option_cases.json
+# name: (mpcg_params option fields, reference keys[, keys kept in the comparison's baseline
+# [, options kept in it: the options that enable the one the case is about]])
+ACC = dict(acceptable_tol=1e-3, acceptable_iter=3)
+ACC2 = dict(acceptable_tol=1e-2, acceptable_iter=2)
+OPTION_CASES = {
+    "tol_1e-5": (dict(tol=1e-5), {}),
+    "tol_1e-10": (dict(tol=1e-10), {}),
+    "max_iter_7": (dict(max_iter=7), {}),
+    "max_iter_0": (dict(max_iter=0), {}),
+    "mu_init_1": (dict(mu_init=1.0), {}),
+    "mu_init_1e-3": (dict(mu_init=1e-3), {}),
+    "bound_relax_1e-4": (dict(bound_relax_factor=1e-4), {}),
+    "acceptable_iter_2": (dict(ACC2), {}),
+    "acceptable_tol_1e-3": (dict(ACC), {}),
+    "acceptable_obj_change": (dict(ACC, acceptable_obj_change_tol=1e-6), {}, {}, ACC),
+    "acceptable_constr_viol": (dict(ACC, acceptable_constr_viol_tol=1e-9), {}, {}, ACC),
+    "acceptable_dual_inf": (dict(ACC2, acceptable_dual_inf_tol=1e-4), {}, {}, ACC2),
+    "acceptable_compl_inf": (dict(ACC2, acceptable_compl_inf_tol=1e-7), {}, {}, ACC2),
+    "kappa_soc_0.5": (dict(kappa_soc=0.5), {}),
+    "max_soc_1": (dict(max_soc=1), {}),
+    "watchdog_trigger_3": (dict(watchdog_shortened_iter_trigger=3), {}),
+    "watchdog_trial_max_1": (dict(watchdog_trial_iter_max=1), {}),
+    "soft_resto_factor_0": (dict(soft_resto_pderror_reduction_factor=0.0), {}),
+    "soft_resto_factor_0.5": (dict(soft_resto_pderror_reduction_factor=0.5), {}),
+    "max_soft_resto_iters_1": (dict(max_soft_resto_iters=1), {}),
+    "obj_max_inc_0.5": (dict(obj_max_inc=0.5), {}),
+    "max_filter_resets_0": (dict(max_filter_resets=0), {}),
+    "filter_reset_trigger_1": (dict(filter_reset_trigger=1), {}),
+    "filter_reset_trigger_2": (dict(filter_reset_trigger=2, max_filter_resets=1), {}),
+    "tiny_step": (dict(tiny_step_tol=1e-4, tiny_step_y_tol=1e3), {}),
+    "dual_inf_tol_1e-9": (dict(dual_inf_tol=1e-9), {}),
+    "constr_viol_tol_1e-12": (dict(constr_viol_tol=1e-12), {}),
+    # (below tol: the barrier parameter's floor follows it, tests/test_option_matrix.py's docstring)
+    "compl_inf_tol_1e-9": (dict(compl_inf_tol=1e-9), {}),
+    "no_restoration": (dict(no_restoration=1), {}),
+    "max_cpu_time": (dict(max_cpu_time=0.005), {}),
+    "ref_cte": ({}, dict(REF_CTE=0.3)),
+    "ref_etheta": ({}, dict(REF_ETHETA=0.2)),
+    "ref_negative": ({}, dict(REF_CTE=-0.3, REF_ETHETA=-0.2)),
+    "dt_0.05": ({}, dict(DT=0.05)),
+    "dt_0.25": ({}, dict(DT=0.25)),
+    "ref_v": ({}, dict(REF_V=0.3)),
+    "w_v_0": ({}, dict(W_V=0.0)),
+    "w_cte_0": ({}, dict(W_CTE=0.0)),
+    "w_epsi_0": ({}, dict(W_EPSI=0.0)),
+    "w_angvel_w_a_0": ({}, dict(W_ANGVEL=0.0, W_A=0.0)),
+    "w_dangvel_7": ({}, dict(W_DANGVEL=7.0, W_DA=0.0)),
+    "w_da_7": ({}, dict(W_DANGVEL=0.0, W_DA=7.0)),
+    "maxthr": ({}, dict(MAXTHR=0.3)),
+    "angvel": ({}, dict(ANGVEL=0.2)),
+    "angvel_maxthr": ({}, dict(ANGVEL=0.2, MAXTHR=2.5)),
+    "bound_3": ({}, dict(BOUND=3.0)),
+    "bound_1e6": ({}, dict(BOUND=1e6)),
+    "model_bicycle": ({}, dict(MODEL=1, LF=0.5, ANGVEL=0.5)),
+    "lf_0.2": ({}, dict(LF=0.2), dict(MODEL=1, LF=0.5)),
+    "lf_2": ({}, dict(LF=2.0, REF_ETHETA=0.1, DT=0.05), dict(MODEL=1, LF=0.5)),
+    "steps_7": ({}, dict(STEPS=7, REF_CTE=0.3, DT=0.2)),
+}
+# the cases tests/test_gpu_options.py runs across the kernel's instance shapes, and the shapes
+SHAPE_CASES = ("max_iter_7", "mu_init_1", "acceptable_iter_2", "tiny_step", "bound_relax_1e-4", "filter_resets_off")
+SHAPE_EXTRA = {"filter_resets_off": (dict(filter_reset_trigger=1, soft_resto_pderror_reduction_factor=0.0), {})}
+SHAPES = {"N33": dict(STEPS=33), "N40": dict(STEPS=40), "N48": dict(STEPS=48), "N65": dict(STEPS=65),
+          "bicycle_N25": dict(STEPS=25, MODEL=1, LF=0.5, ANGVEL=0.5),
+          "bicycle_N33": dict(STEPS=33, MODEL=1, LF=0.5, ANGVEL=0.5),
+          "bicycle_N40": dict(STEPS=40, MODEL=1, LF=0.5, ANGVEL=0.5),
+          "bicycle_N48": dict(STEPS=48, MODEL=1, LF=0.5, ANGVEL=0.5)}
+PARK_CANDIDATES = {"tol_1e-5": dict(tol=1e-5), "mu_init_1e-3": dict(mu_init=1e-3),
+                   "watchdog_trigger_3": dict(watchdog_shortened_iter_trigger=3),
+                   "filter_reset_trigger_1": dict(filter_reset_trigger=1), "dual_inf_tol_1e-9": dict(dual_inf_tol=1e-9)}
+MAX_ROW_ITERS = 120
+_BASELINES = {}
+
+
+def _scan(case, idx, want=6, pad=2, total=4, need_status=(), max_iters=MAX_ROW_ITERS):
+    """Rows of the infinity-set indices idx for a case: those on which the case acts (status,
+    iteration count, or u0 by more than 1e-9 against the baseline) and on which the oracle's
+    status and iteration count are the same with the dense solve, the structured solve and one
+    refinement step; at most `want` of them (one of every ending first, then the shortest), plus
+    `pad` well-conditioned rows on which it does not act (more, up to `total` rows in all).  The structured oracle (4x faster)
+    screens, the dense oracle decides."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import test_option_matrix as T
+
+    nt = os.cpu_count() or 8
+    st, cf = infinity.make_problems(np.asarray(idx, dtype=np.int64))
+    key = (json.dumps([T.case_params(case, baseline=True), case.get("baseline_options", {})], sort_keys=True), len(idx),
+           int(np.asarray(idx).sum()))
+    if key not in _BASELINES:  # (the defaults' results over a range: once)
+        _BASELINES[key] = T.oracle_case(O, case, st, cf, baseline=True, threads=nt, kkt_structured=1)
+    d = _BASELINES[key]
+    r = T.oracle_case(O, case, st, cf, threads=nt, kkt_structured=1)
+    act = T.acting_rows(r, d) & (r["iters"] <= max_iters)
+    # candidates: every acting row (up to 32, rare endings first) and a few that do not act
+    order = sorted(np.flatnonzero(act), key=lambda b: (r["status"][b] == 1, r["iters"][b]))[:32]
+    cand = np.array(order + list(np.flatnonzero(~act & (r["iters"] <= max_iters))[:max(pad, total) + 2]), dtype=np.int64)
+    if len(cand) == 0:
+        return [], [], {}
+    cst, ccf = st[cand], cf[cand]
+    dd = T.oracle_case(O, case, cst, ccf, baseline=True, threads=nt)
+    rr = T.oracle_case(O, case, cst, ccf, threads=nt)
+    ok = np.ones(len(cand), bool)
+    for kw in (dict(kkt_structured=1), dict(refine_steps=1)):
+        v = T.oracle_case(O, case, cst, ccf, threads=nt, **kw)
+        ok &= (v["status"] == rr["status"]) & (v["iters"] == rr["iters"])
+    acts = T.acting_rows(rr, dd)
+    good = [i for i in range(len(cand)) if ok[i] and acts[i]]
+    chosen = []
+    for s in list(need_status) + sorted(set(rr["status"][good].tolist())):  # one of every ending first
+        for i in good:
+            if rr["status"][i] == s and i not in chosen:
+                chosen.append(i)
+                break
+    for i in sorted(good, key=lambda i: rr["iters"][i]):
+        if len(chosen) >= want:
+            break
+        if i not in chosen:
+            chosen.append(i)
+    chosen = chosen[:want]
+    quiet = [i for i in range(len(cand)) if ok[i] and not acts[i]][:max(pad, total - len(chosen))]
+    info = dict(acting=len(good), status=sorted(set(rr["status"][chosen].tolist())),
+                resto=int((rr["diag"][chosen + quiet, 3] > 0).sum()) if chosen + quiet else 0)
+    return [int(np.asarray(idx)[cand[i]]) for i in chosen], [int(np.asarray(idx)[cand[i]]) for i in quiet], info
+
+
+def _fp32_rows():
+    """Rows of the two fixtures for the fp32 solver alone (tests/test_gpu_options.py), chosen with
+    the host emulation's float solver (wide_host_check.cpp, HOST_T = float) under FP32_OPTIONS
+    without restoration: 8 rows that need more than 5 iterations, on the infinity fixture four of
+    them ended at an acceptable point by acceptable_iter 1 with acceptable_tol 1e-1."""
+    import tempfile
+
+    import test_core_host as H
+    from conftest import load_npz, params_from_array
+
+    out = {}
+    with tempfile.TemporaryDirectory() as d:
+        exe = os.path.join(d, "whc32")
+        subprocess.check_call(["g++", "-O2", "-std=c++20", "-w", "-pthread", "-DHOST_T=float", "-o", exe,
+                               os.path.join(ROOT, "tests", "native", "wide_host_check.cpp")])
+        v, inf = load_npz("variants.npz"), load_npz("infinity_N20.npz")
+        for name, par, st, cf in (("N40", v["N40__params"], v["N40__state"], v["N40__coeffs"]),
+                                  ("infinity", inf["params"], inf["state"], inf["coeffs"])):
+            P = params_from_array(par)
+            res = {}
+            for acc_iter in (15, 1):
+                o = H.fp32_opts(O, P["STEPS"])
+                o.restoration, o.acceptable_iter = 0, acc_iter
+                if acc_iter == 1:
+                    o.acceptable_tol = 1e-1
+                res[acc_iter] = H.run_harness(exe, P, st, cf, opts=o)
+            long_ = res[15]["iters"] > 5
+            acc = np.flatnonzero(long_ & (res[1]["status"] == 4))[:4].tolist()
+            rest = [int(b) for b in np.flatnonzero(long_ & (res[1]["status"] != 4)) if b not in acc][:8 - len(acc)]
+            out[name] = dict(rows=sorted(rest + acc), acceptable=len(acc))
+            print("fp32", name, out[name], flush=True)
+    return out
+
+
+def option_cases():
+    """tests/golden/option_cases.json, all of it: for every case of OPTION_CASES the rows it runs
+    on, found with the oracle over growing ranges of the infinity set (the features sets' indices
+    and 0..255 first, then 0..8191, then 0..65535; a case without an acting row in all of them and
+    in the features sets at N = 40 is recorded inert); the same per kernel instance shape; the
+    restoration sets' rows for options across a park; the fp32 solver's rows."""
+    path = os.path.join(HERE, "option_cases.json")
+    if not os.path.exists(path):  # (tests/test_option_matrix.py, whose helpers the scan uses, reads it)
+        with open(path, "w") as f:
+            json.dump(dict(cases=[], shapes={}, park={}, fp32={}), f)
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    feat20 = FEATURE_SETS["N20"][1] + FEATURE_SETS["resto_N20"][1]
+    feat40 = FEATURE_SETS["N40"][1] + FEATURE_SETS["resto_N40"][1]
+    cases = []
+    for name, spec in OPTION_CASES.items():
+        opts, par = spec[0], spec[1]
+        case = dict(name=name, options=opts, params=par)
+        if len(spec) > 2 and spec[2]:
+            case["baseline_params"] = spec[2]
+        if len(spec) > 3:
+            case["baseline_options"] = spec[3]
+        pools = [sorted(set(feat20) | set(range(256))), np.arange(8192), np.arange(65536)]
+        rows, quiet, info = [], [], {}
+        for pool in pools:  # (a larger range while fewer than three rows act)
+            found = _scan(case, pool)
+            if len(found[0]) > len(rows):
+                rows, quiet, info = found
+            if len(rows) >= 3:
+                break
+        if not rows and "STEPS" not in par:  # the features sets at N = 40 (watchdog, soft restoration)
+            c40 = dict(case, params=dict(par, STEPS=40), baseline_params=dict(case.get("baseline_params", {}), STEPS=40))
+            rows, quiet, info = _scan(c40, feat40)
+            if rows:
+                case = c40
+        if rows:
+            case["rows"] = {"infinity": rows + quiet}
+        else:
+            case["inert"] = True
+            case["scanned"] = "infinity 0..65535, features N20, features N40"
+            case["rows"] = {"infinity": feat20[:8]}
+        print(name, case["rows"], info, flush=True)
+        cases.append(case)
+    out = dict(cases=cases)
+    # the same scan per instance shape (rows 0..1023 of the infinity set, 6 rows each)
+    shapes = {}
+    for sname, par in SHAPES.items():
+        for cname in SHAPE_CASES:
+            opts = (OPTION_CASES.get(cname) or SHAPE_EXTRA[cname])[0]
+            case = dict(name=f"{sname}/{cname}", options=opts, params=par, baseline_params=par)
+            need = {"acceptable_iter_2": (4,), "tiny_step": (3,)}.get(cname, ())
+            rows, quiet, info = _scan(case, np.arange(1024), want=5, pad=1, total=6, need_status=need)
+            print(case["name"], rows, quiet, info, flush=True)
+            shapes.setdefault(sname, {})[cname] = dict(options=opts, rows=(rows + quiet)[:6])
+    out["shapes"] = dict(params=SHAPES, cases=shapes)
+    # options across a park: per restoration set the rows on which the option acts (up to 4),
+    # filled up to 4 with rows on which it does not; kept where the option acts on the set and at
+    # least two of the rows still enter the restoration phase under it (a park area of one entry
+    # then overflows)
+    park = {}
+    for cname, opts in PARK_CANDIDATES.items():
+        for sname in ("resto_N20", "resto_N40"):
+            P, idx = FEATURE_SETS[sname]
+            case = dict(name=f"{sname}/{cname}", options=opts, params=dict(STEPS=P["STEPS"]),
+                        baseline_params=dict(STEPS=P["STEPS"]))
+            rows, quiet, info = _scan(case, idx, want=4, pad=0, max_iters=400)
+            print(case["name"], rows, quiet, info, flush=True)
+            if rows and info.get("resto", 0) >= 2:
+                park.setdefault(cname, {})[sname] = dict(rows=[idx.index(i) for i in rows + quiet], acting=len(rows),
+                                                         resto=info["resto"])
+    out["park"] = park
+    out["fp32"] = _fp32_rows()
+    with open(path, "w") as f:
+        json.dump(out, f, indent=1)
+
+
 if __name__ == "__main__":
     O.build(force=True)
+    if sys.argv[1:2] == ["option_cases"]:  # (not part of "all": a scan of several minutes)
+        option_cases()
+        sys.exit(0)
     sets = set(sys.argv[1:]) or {"hs071", "preprocess", "infinity", "variants", "bicycle", "features", "cppad"}
     if "hs071" in sets:
         hs071()

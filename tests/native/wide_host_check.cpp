@@ -16,7 +16,7 @@
 //         acceptable_compl_inf_tol acceptable_obj_change_tol max_soc kappa_soc wd_trigger
 //         wd_trial_max soft_factor max_soft_iters obj_max_inc max_filter_resets
 //         filter_reset_trigger tiny_step_tol tiny_step_y_tol cpu_iter_budget filter_cap
-//         dual_inf_tol constr_viol_tol compl_inf_tol
+//         dual_inf_tol constr_viol_tol compl_inf_tol mu_init bound_relax_factor no_resto
 //         B, then B x (state[6], coeffs[4])
 // stdout: per problem: status iters obj u0[2] traj[3N] restoration-phases filter-overflows filter-peak
 #include <barrier>
@@ -232,8 +232,6 @@ int main() {
                    &P.ref_eth, &P.ref_v, &P.w_cte, &P.w_eth, &P.w_v, &P.w_w, &P.w_a, &P.w_dw, &P.w_da, &P.max_w,
                    &P.max_a, &P.bound, &P.tol, &P.max_iter) != 17)
         return 1;
-    P.bound_relax_factor = 1e-8;
-    P.mu_init = 0.1;
     P.filter_cap = 64;
     P.model = 0;
     P.lf = 0.5;
@@ -245,7 +243,9 @@ int main() {
                    &P.obj_max_inc, &P.max_filter_resets, &P.filter_reset_trigger, &P.tiny_step_tol,
                    &P.tiny_step_y_tol, &P.cpu_iter_budget, &P.filter_cap) != 19)
         return 1;
-    if (std::scanf("%lf %lf %lf", &P.dual_inf_tol, &P.constr_viol_tol, &P.compl_inf_tol) != 3) return 1;
+    if (std::scanf("%lf %lf %lf %lf %lf %d", &P.dual_inf_tol, &P.constr_viol_tol, &P.compl_inf_tol, &P.mu_init,
+                   &P.bound_relax_factor, &P.no_resto) != 6)
+        return 1;
     long B;
     if (std::scanf("%ld", &B) != 1) return 1;
     const bool two_phase = std::getenv("MPCG_HOST_TWO_PHASE") && std::atoi(std::getenv("MPCG_HOST_TWO_PHASE")) != 0;

@@ -89,6 +89,89 @@ def test_param_defaults_and_keys(libmpcg):
     assert libmpcg.mpcg_params_check(C.byref(p)) < 0
 
 
+# field: (value just outside its domain, the edge value inside); include/mpcg.h, mpcg_params_check
+PARAM_DOMAIN = {
+    "steps": (1, 2),
+    "filter_cap": (0, 1),
+    "tol": (0.0, 5e-324),
+    "max_iter": (-1, 0),
+    "acceptable_iter": (-1, 0),
+    "max_soc": (-1, 0),
+    "watchdog_shortened_iter_trigger": (-1, 0),
+    "watchdog_trial_iter_max": (-1, 0),
+    "max_soft_resto_iters": (-1, 0),
+    "max_filter_resets": (-1, 0),
+    "filter_reset_trigger": (0, 1),
+    "kappa_soc": (0.0, 5e-324),
+    "soft_resto_pderror_reduction_factor": (-5e-324, 0.0),
+    "tiny_step_tol": (-5e-324, 0.0),
+    "dual_inf_tol": (0.0, 5e-324),
+    "constr_viol_tol": (0.0, 5e-324),
+    "compl_inf_tol": (0.0, 5e-324),
+    "bound_relax_factor": (-5e-324, 0.0),
+    "mu_init": (0.0, 5e-324),
+    "max_cpu_time": (0.0, 5e-324),
+    "dt": (0.0, 5e-324),
+    "max_angvel": (0.0, 5e-324),
+    "max_throttle": (0.0, 5e-324),
+    "bound": (0.0, 5e-324),
+    "w_cte": (-5e-324, 0.0),
+    "w_etheta": (-5e-324, 0.0),
+    "w_v": (-5e-324, 0.0),
+    "w_angvel": (-5e-324, 0.0),
+    "w_accel": (-5e-324, 0.0),
+    "w_angvel_d": (-5e-324, 0.0),
+    "w_accel_d": (-5e-324, 0.0),
+    "model": (2, 1),
+    "precision": (2, 1),
+    "no_restoration": (2, 1),
+}
+
+
+@pytest.mark.parametrize("field", list(PARAM_DOMAIN))
+def test_params_check_domain_edges(libmpcg, field):
+    """mpcg_params_check refuses a value just outside a field's domain and accepts the edge
+    value inside it (every other field at the plugin's defaults)."""
+    from mpc_ros_amd import _lib
+
+    def check(**fields):
+        p = _lib.MpcgParams()
+        assert libmpcg.mpcg_params_plugin_default(C.byref(p)) == 0
+        p.wheelbase = 0.5
+        for k, v in fields.items():
+            setattr(p, k, v)
+        return libmpcg.mpcg_params_check(C.byref(p))
+
+    assert check() == 0
+    outside, inside = PARAM_DOMAIN[field]
+    assert check(**{field: outside}) < 0 and libmpcg.mpcg_last_error()
+    assert check(**{field: inside}) == 0
+
+
+def test_params_check_domain_upper_edges_and_couplings(libmpcg):
+    """The upper ends (filter_cap 1024 / 1025, steps 4096 / 4097; the lower ends are above), the negative values of
+    the two-valued fields, and the fields that are refused together: the bicycle needs a
+    wheelbase, and the fp32 solver runs the differential drive only."""
+    from mpc_ros_amd import _lib
+
+    def check(**fields):
+        p = _lib.MpcgParams()
+        libmpcg.mpcg_params_plugin_default(C.byref(p))
+        for k, v in fields.items():
+            setattr(p, k, v)
+        return libmpcg.mpcg_params_check(C.byref(p))
+
+    assert check(filter_cap=1024) == 0 and check(filter_cap=1025) < 0
+    assert check(steps=4096) == 0 and check(steps=4097) < 0
+    assert check(model=-1) < 0 and check(precision=-1) < 0 and check(no_restoration=-1) < 0
+    assert check(model=1, wheelbase=0.0) < 0 and check(model=1, wheelbase=5e-324) == 0
+    assert check(precision=1, model=0) == 0 and check(precision=1, model=1, wheelbase=0.5) < 0
+    assert check(precision=0, model=1, wheelbase=0.5) == 0
+    for f in ("dt", "w_cte", "w_accel_d"):  # (finite where the check says so)
+        assert check(**{f: float("inf")}) < 0 and check(**{f: float("nan")}) < 0
+    assert check(tol=float("nan")) < 0 and check(kappa_soc=float("nan")) < 0
+
+
 def test_workspace_bytes(libmpcg):
     """Workspace slots per resident wavefront (not per problem), in 8 equal per-XCD
     partitions of at least min(B, 32), and a park area for the problems that enter the

@@ -29,17 +29,19 @@ def subset(g, rows):
     return {k: g[k][rows] for k in keys if k in g}
 
 
-def opts_line(o) -> str:
-    """The harness's Ipopt-option line from an oracle IpmOpts (same values both sides)."""
+def opts_line(o, filter_cap=64) -> str:
+    """The harness's Ipopt-option lines from an oracle IpmOpts (same values both sides;
+    restoration = 0 is the core's no_resto = 1)."""
     return (f"{o.acceptable_tol!r} {o.acceptable_iter} {o.acceptable_dual_inf_tol!r} {o.acceptable_constr_viol_tol!r} "
             f"{o.acceptable_compl_inf_tol!r} {o.acceptable_obj_change_tol!r} {o.max_soc} {o.kappa_soc!r} "
             f"{o.watchdog_shortened_iter_trigger} {o.watchdog_trial_iter_max} "
             f"{o.soft_resto_pderror_reduction_factor!r} {o.max_soft_resto_iters} {o.obj_max_inc!r} "
             f"{o.max_filter_resets} {o.filter_reset_trigger} {o.tiny_step_tol!r} {o.tiny_step_y_tol!r} "
-            f"{o.cpu_iter_budget} 64\n{o.dual_inf_tol!r} {o.constr_viol_tol!r} {o.compl_inf_tol!r}")
+            f"{o.cpu_iter_budget} {int(filter_cap)}\n{o.dual_inf_tol!r} {o.constr_viol_tol!r} {o.compl_inf_tol!r} "
+            f"{o.mu_init!r} {o.bound_relax_factor!r} {0 if o.restoration else 1}")
 
 
-def run_harness(exe, P, state, coeffs, opts=None, env=None):
+def run_harness(exe, P, state, coeffs, opts=None, env=None, filter_cap=64):
     from oracle import pyoracle as O
 
     N = int(P["STEPS"])
@@ -47,7 +49,7 @@ def run_harness(exe, P, state, coeffs, opts=None, env=None):
     hdr = (f"{N} {P['DT']!r} {P['REF_CTE']!r} {P['REF_ETHETA']!r} {P['REF_V']!r} {P['W_CTE']!r} {P['W_EPSI']!r} "
            f"{P['W_V']!r} {P['W_ANGVEL']!r} {P['W_A']!r} {P['W_DANGVEL']!r} {P['W_DA']!r} {P['ANGVEL']!r} "
            f"{P['MAXTHR']!r} {P['BOUND']!r} {o.tol!r} {o.max_iter}\n{int(P.get('MODEL', 0))} {float(P.get('LF', 0.5))!r}\n"
-           f"{opts_line(o)}\n{len(state)}\n")
+           f"{opts_line(o, filter_cap)}\n{len(state)}\n")
     body = "\n".join(" ".join(repr(float(v)) for v in np.concatenate([state[b], coeffs[b]]))
                      for b in range(len(state)))
     out = subprocess.run([exe], input=hdr + body + "\n", capture_output=True, text=True, check=True,
@@ -85,12 +87,17 @@ def compare(r, g, atol=1e-9, iters_exact=1.0):
 # wavefront: stage-parallel sweeps, 64-lane Riccati) with 64 fibers standing in for the
 # lanes.  Summation orders differ from the oracle's (tree reductions), so the
 # comparison is to rounding: same status and iteration count, controls within 1e-9.
+_harness_exe = []  # (built once per session: tests/test_option_matrix.py uses the same fixture)
+
+
 @pytest.fixture(scope="module")
 def wide_harness(tmp_path_factory):
-    exe = str(tmp_path_factory.mktemp("whc") / "wide_host_check")
-    subprocess.check_call(["g++", "-O2", "-std=c++20", "-w", "-pthread", "-o", exe,
-                           os.path.join(ROOT, "tests", "native", "wide_host_check.cpp")])
-    return exe
+    if not _harness_exe:
+        exe = str(tmp_path_factory.mktemp("whc") / "wide_host_check")
+        subprocess.check_call(["g++", "-O2", "-std=c++20", "-w", "-pthread", "-o", exe,
+                               os.path.join(ROOT, "tests", "native", "wide_host_check.cpp")])
+        _harness_exe.append(exe)
+    return _harness_exe[0]
 
 
 def test_wide_core_matches_oracle_infinity_subset(wide_harness, infinity_golden):

@@ -1,0 +1,265 @@
+"""GPU: every solver option and problem parameter through the C-ABI against the oracle.
+
+The default-options kernel instances compile the reference's Ipopt options in as constants; a
+caller who changes one option runs the general instances and k_resume_wide, which read them
+from WideArgs.  tests/golden/option_cases.json (tests/test_option_matrix.py: the table, its
+rows and the CPU side) is run here through BatchSolver -- mpcg_params, mpcg_api.cpp's to_ipm,
+the general instance -- against the oracle live under the same options, at test_gpu_parity's
+tolerance with iteration counts exact; then a few strong options across the instance shapes,
+across a park and its overflow, filter_cap, the fp32 solver alone, and a handle whose
+parameters change between solves.
+"""
+from __future__ import annotations
+
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+from conftest import ROOT
+from test_core_host import FILTER_PEAKS, fp32_opts, run_harness
+from test_gpu_parity import check_against, solver_for, torch_cuda  # noqa: F401
+from test_option_matrix import CASES, TABLE, case_params, case_problems, oracle_case, oracle_opts
+
+pytestmark = pytest.mark.gpu
+
+OUT = ("u0", "traj", "status", "iters", "obj")
+_device_status = {}
+
+
+def general_instance(s):
+    """k_solve_wide<model, split, type, stage blocks, default options, waves per SIMD>: the
+    fifth is false."""
+    k = s.last_kernel
+    assert k.startswith("k_solve_wide<") and k[:-1].split(",")[4] == "false", k
+
+
+# ------------------------------------------------------------------ a. the matrix
+@pytest.mark.parametrize("name", list(CASES))
+def test_case_matches_oracle(torch_cuda, oracle, features_golden, name):  # noqa: F811
+    case = CASES[name]
+    P = case_params(case)
+    st, cf = case_problems(case, features_golden)
+    ref = oracle_case(oracle, case, st, cf, threads=16)
+    # (an option equal to its default would take the default-options instance: one that cannot
+    # act, as in test_default_option_instance_equals_general, keeps the case on the general one)
+    opts = dict(case["options"])
+    if set(opts) <= {"max_cpu_time"}:  # (the iteration budget is an argument of every instance)
+        opts["acceptable_obj_change_tol"] = 1e30
+    s = solver_for(P, **opts)
+    r = s.solve(st, cf)
+    general_instance(s)
+    check_against(r, ref, min_same_iters=1.0)
+    _device_status[name] = set(r["status"].tolist())
+    if case.get("inert"):
+        d = solver_for(case_params(case, baseline=True))
+        rd = d.solve(st, cf)
+        assert d.last_kernel[:-1].split(",")[4] == "true", d.last_kernel
+        for k in OUT:
+            np.testing.assert_array_equal(r[k], rd[k])
+
+
+def test_device_status_coverage(torch_cuda, oracle, features_golden):  # noqa: F811
+    """The iteration limit (2), a tiny step (3), an acceptable point (4) and local
+    infeasibility (5) each end some row of the table on the device itself."""
+    for name in CASES:  # (alone or in another order: the cases not yet run)
+        if name not in _device_status:
+            case = CASES[name]
+            st, cf = case_problems(case, features_golden)
+            r = solver_for(case_params(case), **case["options"]).solve(st, cf)
+            _device_status[name] = set(r["status"].tolist())
+    seen = set().union(*_device_status.values())
+    assert {1, 2, 3, 4, 5} <= seen, seen
+
+
+# ------------------------------------------------------------------ b. instance shapes
+SHAPE_KERNEL = {
+    "N33": "k_solve_wide<0,false,double,1,false,2>",
+    "N40": "k_solve_wide<0,false,double,1,false,2>",
+    "N48": "k_solve_wide<0,false,double,1,false,1>",
+    "N65": "k_solve_wide<0,false,double,2,false,1>",
+    "bicycle_N25": "k_solve_wide<1,true,double,1,false,2>",
+    "bicycle_N33": "k_solve_wide<1,false,double,1,false,2>",
+    "bicycle_N40": "k_solve_wide<1,false,double,1,false,2>",
+    "bicycle_N48": "k_solve_wide<1,false,double,1,false,1>",
+}
+SHAPE_ENDING = {"max_iter_7": 2, "acceptable_iter_2": 4, "tiny_step": 3}
+
+
+@pytest.mark.parametrize("shape", list(SHAPE_KERNEL))
+def test_options_across_instance_shapes(torch_cuda, oracle, shape):  # noqa: F811
+    """Six options that act strongly on each general instance shape (N = 33 and 40: unsplit,
+    two wavefronts per SIMD -- the problem's LDS stays below 32 KB; N = 48: more than 32 KB, the
+    instance allocated for one wavefront per SIMD; N = 65: two stage blocks; the bicycle split
+    at 25, unsplit at 33 and 40, one wavefront per SIMD at 48), rows chosen per shape by the
+    table's scan."""
+    from mpc_ros_amd import infinity, params
+
+    P = dict(params.PLUGIN_DEFAULTS, **TABLE["shapes"]["params"][shape])
+    for cname, c in TABLE["shapes"]["cases"][shape].items():
+        assert len(c["rows"]) == 6, (shape, cname)
+        st, cf = infinity.make_problems(np.asarray(c["rows"], dtype=np.int64))
+        o = oracle_opts(oracle, P["STEPS"], c["options"])
+        ref = oracle.mpc_solve_batch(P, st, cf, opts=o, nthreads=16, diag=True)
+        dflt = oracle.mpc_solve_batch(P, st, cf, opts=oracle.ref_opts(P["STEPS"]), nthreads=16)
+        assert ((ref["status"] != dflt["status"]) | (ref["iters"] != dflt["iters"])
+                | (np.abs(ref["u0"] - dflt["u0"]).max(1) > 1e-9)).any(), (shape, cname)
+        if cname in SHAPE_ENDING:
+            assert (ref["status"] == SHAPE_ENDING[cname]).any(), (shape, cname)
+        s = solver_for(P, **c["options"])
+        r = s.solve(st, cf)
+        assert s.last_kernel == SHAPE_KERNEL[shape], (shape, s.last_kernel)
+        check_against(r, ref, min_same_iters=1.0)
+
+
+# ------------------------------------------------------------------ c. across a park
+PARK_SETS = [(c, n) for c, sets in TABLE["park"].items() for n in sets]
+
+
+@pytest.mark.parametrize("park_capacity", [0, 1])
+@pytest.mark.parametrize("cname,sname", PARK_SETS)
+def test_options_across_a_park(torch_cuda, oracle, features_golden, cname, sname, park_capacity):  # noqa: F811
+    """An option changed on problems that enter the restoration phase: k_resume_wide reads the
+    same options (restoration counts, statuses and iteration counts are the oracle's), also when
+    the park area holds one entry and the others are solved again after the batch.  Every set
+    of the table is one on which the option acts and at least two rows still restore."""
+    opts = CASES[cname]["options"]
+    g = features_golden[sname]
+    rows = np.asarray(TABLE["park"][cname][sname]["rows"])
+    st, cf = g["state"][rows], g["coeffs"][rows]
+    N = int(g["P"]["STEPS"])
+    ref = oracle.mpc_solve_batch(g["P"], st, cf, opts=oracle_opts(oracle, N, opts), nthreads=16, diag=True)
+    dflt = {k: g[k][rows] for k in ("status", "iters", "u0")}
+    assert ((ref["status"] != dflt["status"]) | (ref["iters"] != dflt["iters"])
+            | (np.abs(ref["u0"] - dflt["u0"]).max(1) > 1e-9)).any()
+    resto = ref["diag"][:, 3] > 0
+    assert resto.sum() >= 2
+    s = solver_for(g["P"], **opts)
+    s.set_park_capacity(park_capacity)
+    r = s.solve(st, cf)
+    general_instance(s)
+    check_against(r, ref, min_same_iters=1.0)
+    np.testing.assert_array_equal(r["diag"][:, 2] > 0, resto)
+    if park_capacity == 0:
+        assert (r["diag"][resto, 2] == 1).all()
+    else:
+        assert (r["diag"][:, 2] == 2).any() and (r["diag"][:, 2] == 1).sum() <= 1
+
+
+def test_park_table_covers_options_and_sets():
+    assert len(TABLE["park"]) >= 3 and {n for _, n in PARK_SETS} == {"resto_N20", "resto_N40"}
+
+
+# ------------------------------------------------------------------ d. filter_cap
+@pytest.mark.parametrize("cap", [1, 8, 63, 65, 128])
+def test_filter_cap_does_not_change_results(torch_cuda, features_golden, cap):  # noqa: F811
+    """The filter's LDS part of filter_cap entries and its workspace part (448 more): results
+    are bitwise those of filter_cap 64 and the oracle's (whose filter is unbounded) on the rows
+    whose filters peak at 53, 51 and 196 entries."""
+    for name, peaks in FILTER_PEAKS.items():
+        g = features_golden[name]
+        rows = [int(np.flatnonzero(g["index"] == pid)[0]) for pid in peaks]
+        st, cf = g["state"][rows], g["coeffs"][rows]
+        sub = {k: g[k][rows] for k in ("u0", "traj", "obj", "status", "iters", "diag")}
+        a = solver_for(g["P"]).solve(st, cf)
+        s = solver_for(g["P"], filter_cap=cap)
+        b = s.solve(st, cf)
+        general_instance(s)
+        for k in OUT:
+            np.testing.assert_array_equal(a[k], b[k])
+        np.testing.assert_array_equal(a["diag"][:, [0, 1, 3]], b["diag"][:, [0, 1, 3]])
+        np.testing.assert_array_equal(b["diag"][:, 3], list(peaks.values()))
+        check_against(b, sub, min_same_iters=1.0)
+
+
+# ------------------------------------------------------------------ e. the fp32 solver alone
+@pytest.fixture(scope="module")
+def float_harness(tmp_path_factory):
+    exe = str(tmp_path_factory.mktemp("whc32") / "wide_host_check_f32")
+    subprocess.check_call(["g++", "-O2", "-std=c++20", "-w", "-pthread", "-DHOST_T=float", "-o", exe,
+                           os.path.join(ROOT, "tests", "native", "wide_host_check.cpp")])
+    return exe
+
+
+@pytest.mark.parametrize("name", ["N40", "infinity"])
+def test_fp32_general_instance_under_an_option(torch_cuda, oracle, float_harness, variants_golden,  # noqa: F811
+                                               infinity_golden, name):
+    """dtype "fp32" with no_restoration = 1 runs the fp32 phase alone (its general instance,
+    the only one it has).  max_iter 5: every row ends at the iteration limit after 5.
+    acceptable_iter 2 with acceptable_tol 1e-1: statuses and iteration counts are those of the
+    host emulation's float solver (wide_host_check.cpp built with HOST_T = float) under the same
+    options.  That setting ends no row of either fixture at an acceptable point, in any
+    correct solver: with the fp32 options' tol 1e-3 and compl_inf_tol 1e-2 (the value of
+    acceptable_compl_inf_tol) an iterate is acceptable for at most one iteration before it
+    converges -- the fp64 oracle under the same options ends 0 of the 24 N = 40 rows and 0 of
+    the 288 infinity rows with status 4, the float solver on the host likewise.  With
+    acceptable_iter 1 the oracle ends 19 and the float solver 20 of the infinity rows there
+    (none at N = 40), so the acceptable ending (status 4) is asserted under acceptable_iter 1
+    on the infinity rows, again equal to the host's float solver."""
+    from conftest import params_from_array
+
+    g = variants_golden["N40"] if name == "N40" else infinity_golden
+    P = params_from_array(g["params"])
+    rows = TABLE["fp32"][name]["rows"]  # (8 rows of more than 5 fp32 iterations, chosen by the table's scan)
+    assert len(rows) == 8
+    st, cf = g["state"][rows], g["coeffs"][rows]
+    s = solver_for(P, dtype="fp32", no_restoration=1, max_iter=5)
+    r = s.solve(st, cf)
+    assert ",float," in s.last_kernel and s.last_kernel[:-1].split(",")[4] == "false"
+    assert (r["status"] == 2).all() and (r["iters"] == 5).all()
+    assert (r["diag"][:, 2] == 0).all()  # (no fp64 phase)
+    for acc_iter in (2, 1):
+        r = solver_for(P, dtype="fp32", no_restoration=1, acceptable_iter=acc_iter, acceptable_tol=1e-1).solve(st, cf)
+        assert (r["diag"][:, 2] == 0).all()
+        o = fp32_opts(oracle, int(P["STEPS"]))
+        o.restoration, o.acceptable_iter, o.acceptable_tol = 0, acc_iter, 1e-1
+        h = run_harness(float_harness, P, st, cf, opts=o)
+        np.testing.assert_array_equal(r["status"], h["status"])
+        np.testing.assert_array_equal(r["iters"], h["iters"])
+        if acc_iter == 1 and name == "infinity":
+            assert (r["status"] == 4).any()
+
+
+# ------------------------------------------------------------------ f. a live handle
+def test_reparameterising_a_live_handle(torch_cuda, infinity_golden):  # noqa: F811
+    """set_params between solves on one handle (the reference's dynamic_reconfigure feeds
+    LoadParams between ticks): horizon, model, filter_cap and weights change the kernel
+    instance, the LDS size and the workspace's slot and park-entry sizes (the handle grows its
+    workspace where a step needs more); every solve equals a fresh handle's bitwise, diagnostics
+    included, and launches the same instance."""
+    from mpc_ros_amd import params
+
+    PL = params.PLUGIN_DEFAULTS
+    bike = dict(PL, STEPS=25, MODEL=1, LF=0.5, ANGVEL=0.5)
+    steps = [(PL, {}), (dict(PL, STEPS=40), {}), (bike, {}), (PL, dict(filter_cap=128)),
+             (params.CLASS_DEFAULTS, {}), (dict(PL, STEPS=65), {}), (PL, {})]
+    st, cf = infinity_golden["state"][:8], infinity_golden["coeffs"][:8]
+    live = solver_for(PL)
+    for i, (P, opts) in enumerate(steps):
+        live.set_params(P, **opts)
+        r = live.solve(st, cf)
+        fresh = solver_for(P, **opts)
+        f = fresh.solve(st, cf)
+        for k in OUT + ("diag",):
+            np.testing.assert_array_equal(r[k], f[k], err_msg=f"step {i} {k}")
+        assert live.last_kernel == fresh.last_kernel and live.last_kernel, i
+    np.testing.assert_array_equal(r["u0"], solver_for(PL).solve(st, cf)["u0"])
+    np.testing.assert_allclose(r["u0"], infinity_golden["u0"][:8], rtol=0, atol=1e-7)
+
+
+def test_python_mpc_class_loadparams_between_solves(torch_cuda, infinity_golden, variants_golden):  # noqa: F811
+    """MPC.LoadParams with another STEPS between two Solve calls of one object."""
+    from conftest import params_from_array
+    from mpc_ros_amd.mpc import MPC
+
+    m = MPC()
+    for g in (infinity_golden, variants_golden["N40"], infinity_golden):
+        P = params_from_array(g["params"])
+        m.LoadParams(P)
+        for b in (0, 3):
+            u = m.Solve(g["state"][b], g["coeffs"][b])
+            np.testing.assert_allclose(u, g["u0"][b], rtol=0, atol=1e-7)
+            np.testing.assert_allclose(m.mpc_x, g["traj"][b][0], rtol=0, atol=1e-7)
+            assert len(m.mpc_theta) == P["STEPS"] and m.last_status == g["status"][b]
+            assert m.last_iters == g["iters"][b]
