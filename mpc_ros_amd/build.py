@@ -15,8 +15,8 @@ LIB = os.path.join(HERE, "libmpcg.so")
 SOURCES = [os.path.join(CSRC, f) for f in ("mpcg_wide.hip", "mpcg_wide_inst.hip", "mpcg_track.hip", "mpcg_synth.hip",
                                            "mpcg_api.cpp", "mpcg_multi.cpp", "mpc_planner.cpp")]
 INST = os.path.join(CSRC, "mpcg_wide_inst.hip")
-N_INST = 12  # MPCG_INST groups of mpcg_wide_inst.hip (mpcg_wide_kern.h)
-HEADERS = [os.path.join(CSRC, f) for f in ("ipm_core.h", "wide_core.h", "wave_dev.h", "mpcg_internal.h",
+N_INST = 12  # MPCG_INST groups of mpcg_wide_inst.hip (the instance lists of wide_plan.h)
+HEADERS = [os.path.join(CSRC, f) for f in ("ipm_core.h", "wide_core.h", "wide_plan.h", "wave_dev.h", "mpcg_internal.h",
                                            "mpcg_wide_kern.h")] + [
     os.path.join(ROOT, "include", f) for f in ("mpcg.h", "mpc_planner.h")]
 ARCH = os.environ.get("MPCG_OFFLOAD_ARCH", "gfx950")
@@ -88,7 +88,7 @@ def build(force: bool = False, verbose: bool = False, jobs: int | None = None) -
     # refuses -- mpcg_wide.hip checks sharedSizeBytes == 0)
     flags = [f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC",
              "-mllvm", "-disable-promote-alloca-to-lds", "-mllvm", "-disable-machine-licm",
-             "-Wno-unused-result", "-Wno-unused-value",
+             "-Wno-unused-result", "-Wno-unused-value", "-Wno-c++20-designator",
              f"-I{os.path.join(ROOT, 'include')}", f"-I{CSRC}", "-Rpass-analysis=kernel-resource-usage"]
     # (diagnostic builds only: extra compiler flags, part of the build id)
     flags += [f'-DMPCG_BUILD_ID="MPCG-BUILD-ID:{build_id()}"'] + extra_cflags()

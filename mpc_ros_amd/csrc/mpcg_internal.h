@@ -8,22 +8,20 @@
 #include <string>
 #include <vector>
 
-#include "ipm_core.h"
+#include "wide_plan.h"
 
 namespace mpcg {
 
 // mpcg_last_error()'s message for this thread; returns code
 int set_error(int code, const std::string& msg);
 
-// One problem per wavefront (mpcg_wide.hip): LDS bytes per problem, launch.
-size_t wide_lds_bytes(const IpmParams& P);
+// One problem per wavefront (mpcg_wide.hip; the plan -- instance choice, workspace layout,
+// wide_lds_bytes, kOrderMinBatch -- is wide_plan.h).
 // HBM workspace of a batch of B (watchdog, acceptable point, second-order corrections,
 // soft restoration, the restoration phase: rare paths that must not cost LDS): one slot
-// per wavefront the device holds resident (wide_slots), claimed by each problem's wavefront
+// per wavefront the device holds resident, claimed by each problem's wavefront
+// (SolveLayout::total for the current device)
 size_t wide_spill_bytes(const IpmParams& P, int64_t B);
-int64_t wide_slots(const IpmParams& P, int64_t B);
-// batches beyond the resident wavefronts are solved in expected-longest-first order
-constexpr int64_t kOrderMinBatch = 2048;
 // The streams and events a solve forks work onto (each joined back into the caller's stream
 // before the launch returns): aux -- the resume workers of the restoration phase, and the fp32
 // configuration's head (the problems the solve order ranks longest, solved in fp64 while the
@@ -36,8 +34,6 @@ hipError_t launch_wide_solve(const IpmParams& P, int64_t B, const double* state,
                              double* traj, int32_t* status, double* obj, int32_t* iters, int32_t* diag,
                              const int32_t* order, void* spill, size_t spill_bytes, hipStream_t stream,
                              const WideStreams& ws = WideStreams(), const char** kernel_name = nullptr);
-// park-area capacity of a batch of B (problems that enter the restoration phase)
-int64_t wide_park_cap(const IpmParams& P, int64_t B);
 // Solve order (expected-longest first): device buffer bytes for B problems, and the
 // launch that writes the workgroup -> problem map into `buf` (returned in *order).
 size_t wide_sched_bytes(int64_t B);

@@ -1,7 +1,7 @@
 // mpc_ros_amd/csrc/mpcg_wide_inst.hip -- the solver kernel instances, one group per
 // translation unit: build.py compiles this file once per MPCG_INST value (0..11, in
 // parallel) and links the objects into libmpcg.so.  The groups are listed with their
-// instances in mpcg_wide_kern.h (MPCG_WIDE_SOLVE_INSTANCES / MPCG_WIDE_RESUME_INSTANCES).
+// instances in wide_plan.h (MPCG_WIDE_SOLVE_INSTANCES / _RESUME_ / _WARM_INSTANCES).
 #include "mpcg_wide_kern.h"
 
 #ifndef MPCG_INST

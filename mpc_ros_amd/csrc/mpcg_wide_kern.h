@@ -1,7 +1,8 @@
 // mpc_ros_amd/csrc/mpcg_wide_kern.h -- the solver kernels of mpcg_wide.hip (one problem per
 // wavefront, wide_core.h) as templates.  Each instance is compiled in its own translation
-// unit (mpcg_wide_inst.hip, one group per MPCG_INST value, built in parallel); the
-// dispatcher in mpcg_wide.hip reaches them through solve_kernel_fn / resume_kernel_fn.
+// unit (mpcg_wide_inst.hip, one group per MPCG_INST value, built in parallel; the lists of
+// instances and groups are in wide_plan.h); the dispatcher in mpcg_wide.hip reaches them
+// through solve_kernel_fn / resume_kernel_fn / warm_kernel_fn.
 //
 // One workgroup = one wavefront = one problem; the problem's whole state lives in
 // the workgroup's LDS (WideLayout: 19.0 KB at N = 20, i.e. 8 problems resident per
@@ -14,6 +15,7 @@
 #include "mpcg_internal.h"
 #include "wave_dev.h"
 #include "wide_core.h"
+#include "wide_plan.h"
 
 namespace mpcg {
 
@@ -91,7 +93,6 @@ __device__ __forceinline__ void block_done(int32_t* done) {
     if (threadIdx.x == 0) atomicAdd(done, 1);
 }
 
-constexpr int kXcds = 8;  // (MI355X; the runtime's count is used where it can say: device_xccs)
 // The XCD the wavefront runs on (HW_REG_XCC_ID; 0..7 on MI355X in SPX mode), reduced to the
 // device's nxcc XCDs (a partitioned device reports fewer)
 __device__ __forceinline__ int xcc_id(int nxcc) {
@@ -150,7 +151,7 @@ template <class Solver>
 __device__ __forceinline__ void write_out(const WideArgs& a, Solver& S, int64_t p, int parked);
 
 // WPE: wavefronts per SIMD the register allocation is for -- 2 (256 VGPRs), 1 (512) for the
-// instances whose LDS per problem allows at most 4 problems per CU anyway (wide_kernel), or
+// instances whose LDS per problem allows at most 4 problems per CU anyway (wide_plan.h), or
 // 3 (168 VGPRs) for the fp32 solver (N <= 64), whose LDS per problem leaves room for more
 // than 8 problems per CU (N = 20: 9.5 KB, 12 per CU; N = 40: 14.8 KB, 11): with 68 VGPRs
 // spilled the split instance is still 13 % faster than at 2 per SIMD
@@ -436,54 +437,19 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 1)))
 // k_solve_wide<MODEL, SPLIT, T, NB, DEFOPT, WPE> / k_resume_wide<MODEL, SPLIT, T, NB>.
 template <int MODEL, bool SPLIT, class T, int NB, bool DEFOPT, int WPE>
 const void* solve_kernel_fn();
-// (the dispatcher's choice: the instance and its name, "k_solve_wide<M,S,T,NB,D,W>")
+// (the dispatcher's choice, mpcg_wide.hip: the instance of a key -- wide_plan.h solve_key /
+// resume_key / warm_key -- and its name, "k_solve_wide<M,S,T,NB,D,W>"; fn null: not in the library)
 struct WideInst {
     const void* fn;
     const char* name;
 };
 WideInst wide_kernel(const IpmParams& P, int64_t B);
-int device_xccs();
 template <int MODEL, bool SPLIT, class T, int NB>
 const void* resume_kernel_fn();
 template <int MODEL, bool SPLIT, class T, int NB, bool DEFOPT, int WPE>
 const void* warm_kernel_fn();
 
-// (group, model, split, type, blocks, default options, waves per SIMD): the instances the
-// library carries; group = the MPCG_INST translation unit that compiles it
-#define MPCG_WIDE_SOLVE_INSTANCES(X)          \
-    X(0, 0, true, double, 1, true, 2)         \
-    X(0, 0, true, double, 1, true, 1)         \
-    X(1, 0, true, double, 1, false, 2)        \
-    X(2, 0, false, double, 1, false, 2)       \
-    X(2, 0, false, double, 1, false, 1)       \
-    X(5, 0, false, double, 1, true, 2)        \
-    X(3, 0, false, double, 2, false, 1)       \
-    X(1, 0, false, double, 2, true, 1)        \
-    X(6, 0, false, double, 1, true, 1)        \
-    X(4, 0, true, float, 1, false, 3)         \
-    X(5, 0, false, float, 1, false, 3)        \
-    X(6, 0, false, float, 2, false, 2)        \
-    X(7, 1, true, double, 1, false, 2)        \
-    X(4, 1, true, double, 1, true, 2)         \
-    X(8, 1, false, double, 1, false, 2)       \
-    X(7, 1, false, double, 1, true, 2)        \
-    X(8, 1, false, double, 1, false, 1)       \
-    X(9, 1, false, double, 2, false, 1)
-// (the fp32 solver's problems that need the restoration phase are solved again in fp64: its
-// resume kernel is the fp64 instance of the same horizon)
-#define MPCG_WIDE_RESUME_INSTANCES(X)         \
-    X(1, 0, true, double, 1)                  \
-    X(2, 0, false, double, 1)                 \
-    X(3, 0, false, double, 2)                 \
-    X(7, 1, true, double, 1)                  \
-    X(8, 1, false, double, 1)                 \
-    X(9, 1, false, double, 2)
-// the fp64 phase of the fp32 configuration (k_warm_wide), default options: per horizon class
-#define MPCG_WIDE_WARM_INSTANCES(X)           \
-    X(10, 0, true, double, 1, true, 2)        \
-    X(10, 0, false, double, 1, true, 2)       \
-    X(11, 0, false, double, 1, true, 1)       \
-    X(11, 0, false, double, 2, true, 1)
+// (the instances the library carries: the lists of wide_plan.h)
 #define MPCG_DECL_SOLVE(g, M, S, T, NB, D, W) template <> const void* solve_kernel_fn<M, S, T, NB, D, W>();
 #define MPCG_DECL_WARM(g, M, S, T, NB, D, W) template <> const void* warm_kernel_fn<M, S, T, NB, D, W>();
 #define MPCG_DECL_RESUME(g, M, S, T, NB) template <> const void* resume_kernel_fn<M, S, T, NB>();

@@ -140,6 +140,13 @@ struct WideLayout {
     MPCG_HD int SP_XSP() const { return SP_EXT() + XS * N; }
     MPCG_HD int SP_FLTR() const { return SP_XSP() + XW * N; }
     MPCG_HD int slot() const { return SP_FLTR() + 2 * FX; }
+    // A parked problem (WideSolver::park): the solver's persistent scalars, its LDS image, then a
+    // restoration workspace.  The fp32 solver's hand-over (WideSolver::handoff_out): a head, then
+    // the iterate w (8N), z_L (8N), z_U (8N), y (6N).  (Here, so that the launch side's
+    // workspace layout -- wide_plan.h -- reads the solver's own figures.)
+    static constexpr int PARK_SCALARS = 32, HANDOFF_HEAD = 4;
+    MPCG_HD int park() const { return PARK_SCALARS + total() + slot(); }
+    MPCG_HD static int handoff(int N_) { return HANDOFF_HEAD + 30 * N_; }
 };
 
 // The original problem's values the restoration phase needs (passed by value into its
@@ -3597,8 +3604,8 @@ struct WideSolver {
     // 1): h[0] 1 if the fp32 solve converged (status 1 or 4: the fp64 solver continues from its
     // iterate) else 0 (it is solved again from the start), h[1] mu, h[2] iterations, then the
     // iterate w (8N), z_L (8N), z_U (8N), y (6N) in float (WideLayout's stage-major order).
-    static constexpr int HANDOFF_HEAD = 4;
-    MPCG_HD static int handoff_elems(int N_) { return HANDOFF_HEAD + 30 * N_; }
+    static constexpr int HANDOFF_HEAD = WideLayout::HANDOFF_HEAD;
+    MPCG_HD static int handoff_elems(int N_) { return WideLayout::handoff(N_); }
     MPCG_HD void handoff_out(float* h) const {
         const int t_ = wv.lane();
         wv.sync();
@@ -4372,8 +4379,8 @@ struct WideSolver {
     // (WideLayout::total()), then a restoration workspace (WideLayout::slot(): the batch
     // kernel's rare-path copies -- of which the acceptable point is kept -- and the restoration
     // phase's records).
-    static constexpr int PARK_SCALARS = 32;
-    MPCG_HD static int park_elems(const WideLayout& L) { return PARK_SCALARS + L.total() + L.slot(); }
+    static constexpr int PARK_SCALARS = WideLayout::PARK_SCALARS;
+    MPCG_HD static int park_elems(const WideLayout& L) { return L.park(); }
     // (scalar 27: the parked problem's index, written with the scalars and checked by the worker
     // that unparks it -- park_entry_ok: an entry read before it was complete, or one left from
     // another launch, is caught before any of its values is used as an index)

@@ -1,0 +1,297 @@
+// mpc_ros_amd/csrc/wide_plan.h -- the launch plan of the wavefront solver (mpcg_wide.hip), as
+// plain arithmetic on (IpmParams, B, slot budget, XCD count): the kernel instances the library
+// carries and the choice among them, and the layout of the HBM workspace.  No GPU runtime: the
+// launch side passes in what only the runtime can say (the occupancy behind the slot budget,
+// the XCD count), and tests/native/wide_plan_check.cpp checks all of it on the host.
+#ifndef MPCG_WIDE_PLAN_H
+#define MPCG_WIDE_PLAN_H
+
+#include <stddef.h>
+#include <stdint.h>
+
+#include <cstdlib>
+
+#include "wide_core.h"
+
+// (group, model, split, type, blocks, default options, waves per SIMD): the instances the
+// library carries; group = the MPCG_INST translation unit that compiles it
+#define MPCG_WIDE_SOLVE_INSTANCES(X)          \
+    X(0, 0, true, double, 1, true, 2)         \
+    X(0, 0, true, double, 1, true, 1)         \
+    X(1, 0, true, double, 1, false, 2)        \
+    X(2, 0, false, double, 1, false, 2)       \
+    X(2, 0, false, double, 1, false, 1)       \
+    X(5, 0, false, double, 1, true, 2)        \
+    X(3, 0, false, double, 2, false, 1)       \
+    X(1, 0, false, double, 2, true, 1)        \
+    X(6, 0, false, double, 1, true, 1)        \
+    X(4, 0, true, float, 1, false, 3)         \
+    X(5, 0, false, float, 1, false, 3)        \
+    X(6, 0, false, float, 2, false, 2)        \
+    X(7, 1, true, double, 1, false, 2)        \
+    X(4, 1, true, double, 1, true, 2)         \
+    X(8, 1, false, double, 1, false, 2)       \
+    X(7, 1, false, double, 1, true, 2)        \
+    X(8, 1, false, double, 1, false, 1)       \
+    X(9, 1, false, double, 2, false, 1)
+// (the fp32 solver's problems that need the restoration phase are solved again in fp64: its
+// resume kernel is the fp64 instance of the same horizon)
+#define MPCG_WIDE_RESUME_INSTANCES(X)         \
+    X(1, 0, true, double, 1)                  \
+    X(2, 0, false, double, 1)                 \
+    X(3, 0, false, double, 2)                 \
+    X(7, 1, true, double, 1)                  \
+    X(8, 1, false, double, 1)                 \
+    X(9, 1, false, double, 2)
+// the fp64 phase of the fp32 configuration (k_warm_wide), default options: per horizon class
+#define MPCG_WIDE_WARM_INSTANCES(X)           \
+    X(10, 0, true, double, 1, true, 2)        \
+    X(10, 0, false, double, 1, true, 2)       \
+    X(11, 0, false, double, 1, true, 1)       \
+    X(11, 0, false, double, 2, true, 1)
+// (an instance's name: mpcg_last_kernel() reports the one a solve launched)
+#define MPCG_SOLVE_NAME(M, S, T, NB, D, W) "k_solve_wide<" #M "," #S "," #T "," #NB "," #D "," #W ">"
+#define MPCG_WARM_NAME(M, S, T, NB, D, W) "k_warm_wide<" #M "," #S "," #T "," #NB "," #D "," #W ">"
+#define MPCG_RESUME_NAME(M, S, T, NB) "k_resume_wide<" #M "," #S "," #T "," #NB ">"
+
+namespace mpcg {
+
+// batches beyond the resident wavefronts are solved in expected-longest-first order
+constexpr int64_t kOrderMinBatch = 2048;
+constexpr int kXcds = 8;  // (MI355X; the runtime's count is used where it can say: device_xccs)
+
+inline size_t round_up(size_t n, size_t m) { return (n + m - 1) / m * m; }
+inline size_t elem_bytes(const IpmParams& P) { return P.precision == 1 ? sizeof(float) : sizeof(double); }
+// LDS bytes per problem
+inline size_t wide_lds_bytes(const IpmParams& P) {
+    return (size_t)WideLayout(P.N, P.filter_cap, P.model).total() * elem_bytes(P);
+}
+
+// ---------------------------------------------------------------- the instances and the choice
+// An instance's template arguments (a resume instance: model, split, blocks; the rest zero).
+// model < 0: none -- the parameters are refused.
+struct WideKey {
+    int model = -1;
+    bool split = false, f32 = false;
+    int nb = 0;
+    bool defopt = false;
+    int wpe = 0;
+    bool ok() const { return model >= 0; }
+    bool operator==(const WideKey& o) const {
+        return model == o.model && split == o.split && f32 == o.f32 && nb == o.nb && defopt == o.defopt && wpe == o.wpe;
+    }
+};
+#define MPCG_KEY7(g, M, S, T, NB, D, W) WideKey{M, S, sizeof(T) == 4, NB, D, W},
+#define MPCG_KEY5(g, M, S, T, NB) WideKey{M, S, sizeof(T) == 4, NB, false, 0},
+inline constexpr WideKey kSolveKeys[] = {MPCG_WIDE_SOLVE_INSTANCES(MPCG_KEY7)};
+inline constexpr WideKey kResumeKeys[] = {MPCG_WIDE_RESUME_INSTANCES(MPCG_KEY5)};
+inline constexpr WideKey kWarmKeys[] = {MPCG_WIDE_WARM_INSTANCES(MPCG_KEY7)};
+#undef MPCG_KEY7
+#undef MPCG_KEY5
+template <size_t n>
+inline bool has_key(const WideKey (&keys)[n], const WideKey& k) {
+    for (const WideKey& e : keys)
+        if (e == k) return true;
+    return false;
+}
+
+// The horizon class of a problem: SPLIT (N <= 32: the recursions use both half-waves), NB stage
+// blocks (2 for 64 < N <= 128), and `one`: an fp64 problem of more than 32 KB of LDS (N >= 35;
+// every N > 64) leaves room for at most 4 problems per CU (160 KB), one wavefront per SIMD --
+// its instance is register-allocated for one (512 VGPRs, no spills) instead of two.  (A split
+// problem is never `one`: its instances are allocated for two.)  Refused (ok = false): more
+// than 128 stages, and the fp32 solver on anything but the differential drive.
+struct WideClass {
+    bool ok, split, one;
+    int model, nb;
+};
+inline WideClass wide_class(const IpmParams& P) {
+    WideClass c;
+    c.ok = P.N <= 128 && !(P.precision == 1 && P.model != 0);
+    c.model = P.model == 1 ? 1 : 0;
+    c.split = P.N <= 32;
+    c.nb = P.N > 64 ? 2 : 1;
+    c.one = c.nb == 2 || (!c.split && wide_lds_bytes(P) > 32768);
+    return c;
+}
+
+// A small batch (B <= kLoneBatch) runs the benchmark configuration's instance allocated for
+// one wavefront per SIMD as well: its time is set by its longest problem at the
+// lone-wavefront rate, which the 512-VGPR allocation (no spills) shortens (B = 4,096, the
+// BASELINE's configs[1]: 3.02 -> 2.93 ms; B = 1,024 is held at one wavefront per SIMD).
+constexpr int64_t kLoneBatch = 4096;
+
+// The batch kernel's instance for (P, B); !ok(): none.
+inline WideKey solve_key(const IpmParams& P, int64_t B) {
+    const WideClass c = wide_class(P);
+    if (!c.ok) return WideKey{};
+    WideKey k{c.model, c.split, P.precision == 1, c.nb, false, 2};
+    if (k.f32) {  // (no default-options instance; N <= 64: 3 wavefronts per SIMD, mpcg_wide_kern.h)
+        k.wpe = c.nb == 1 ? 3 : 2;
+        return k;
+    }
+    // (default Ipopt options: the instances that compile them as constants -- the benchmark
+    // configuration, configs[4]'s bicycle, and every fp64 horizon of the differential drive
+    // and the bicycle's 33..64 stages at two wavefronts per SIMD)
+    k.defopt = ipopt_options_are_default(P);
+    const bool bench = c.model == 0 && c.split && k.defopt;  // (the benchmark configuration)
+    if (c.one || (bench && B <= kLoneBatch)) k.wpe = 1;
+    // (no default-options instance -- the bicycle at one wavefront per SIMD: the general one)
+    if (k.defopt && !has_key(kSolveKeys, k)) k.defopt = false;
+    return k;
+}
+// the resume kernel of a solve kernel's instance (the general-options instance also for the
+// default-options one: the two compute bitwise the same); for the fp32 solver the fp64
+// instance of the same horizon (a precision-1 launch parks nothing -- the fp32 phase hands every
+// ending to the fp64 phase, no_restoration = 1 keeps it -- so its workers find nothing and exit)
+inline WideKey resume_key(const IpmParams& P) {
+    const WideClass c = wide_class(P);
+    return c.ok ? WideKey{c.model, c.split, false, c.nb, false, 0} : WideKey{};
+}
+// the fp64 phase's instance (k_warm_wide, default options) for the horizon class of the fp64
+// parameters Pr (fp64_params): the differential drive only
+inline WideKey warm_key(const IpmParams& Pr) {
+    const WideClass c = wide_class(Pr);
+    return c.ok && Pr.model == 0 ? WideKey{0, c.split, false, c.nb, true, c.one ? 1 : 2} : WideKey{};
+}
+
+// ---------------------------------------------------------------- the two-phase configuration
+// The fp32 configuration (mpcg_params.precision 1) runs in two phases: the fp32 solver on the
+// whole batch (its stated options), then the fp64 solver with the reference's Ipopt options on
+// the whole batch again (k_warm_wide) -- from the fp32 solver's converged iterate (a few fp64
+// iterations to Ipopt's tolerance), or from the start where the fp32 solve did not converge
+// (its line search fails where Ipopt would enter the restoration phase, a tiny step, the
+// iteration limit: a float iterate's noise floor).  mpcg_params.no_restoration = 1 keeps the
+// fp32 solver's own ending instead (status 9 where Ipopt would restore).
+inline bool two_phase(const IpmParams& P) { return P.precision == 1 && !P.no_resto; }
+inline IpmParams fp64_params(const IpmParams& P) {
+    IpmParams q = P;
+    q.precision = 0;
+    ipopt_default_options(q);
+    return q;
+}
+// The fp32 configuration's head: the problems the solve order ranks longest (ordered batches only,
+// B / 1024 of them) are solved by the fp64 solver from the start on the aux stream while the fp32
+// phase runs the others -- the longest fp64 solves (through the restoration phase) would otherwise
+// start only with the fp64 phase and set its length (problem 19,304 of the infinity set at N = 40:
+// rank 2 of the order, 217 fp64 iterations, 11.5 ms alone).
+inline int64_t head_count(int64_t B) {
+    int64_t div = 1024;
+#ifdef MPCG_HEAD_ENV
+    // (diagnostic builds only: the head's share of the batch, B / MPCG_HEAD_DIV; 0: no head)
+    if (const char* d = getenv("MPCG_HEAD_DIV")) div = atol(d);
+    if (div <= 0) return 0;
+#endif
+    return B > kOrderMinBatch ? B / div : 0;
+}
+// the head's parameters: the fp64 solver's, with a park entry for every head problem (no
+// park-area overflow: the head's stream never waits for its resume workers' stream)
+inline IpmParams head_params(const IpmParams& P, int64_t K) {
+    IpmParams q = fp64_params(P);
+    q.park_cap = (int)K;
+    return q;
+}
+
+// ---------------------------------------------------------------- the workspace
+constexpr size_t kWsAlign = 256, kLine = 128;  // regions; slots and park entries: whole lines
+
+// Workspace slots for a batch of B: the slot budget -- four times the wavefronts the device can
+// hold resident at once, mpcg_wide.hip slot_budget -- at most B (at least 32 per XCD), in one
+// equal partition per XCD.  A wavefront claims slot blockIdx mod the partition size in its
+// XCD's partition, or the next free one: with the margin, a slow problem still holding a slot
+// rarely makes a later wavefront probe further.
+inline int64_t slot_count(int64_t budget, int64_t B, int nxcc) {
+    if (B <= 0) return 0;
+    const int64_t n = budget < B ? budget : B, floor_ = B < 32 ? B : 32;
+    const int64_t part = (n + nxcc - 1) / nxcc;
+    return (part > floor_ ? part : floor_) * nxcc;
+}
+// the park area: problems that enter the restoration phase (rare: ~5e-5 of the infinity set at
+// N = 20, 5e-4 at N = 40, ~4e-3 with the fp32 solver at N = 40); its capacity is B / 128, at
+// least 256 (P.park_cap > 0: that many, mpcg_set_park_capacity).  Beyond it a problem goes to
+// the overflow list and is solved again from the start after the drain.
+inline int64_t wide_park_cap(const IpmParams& P, int64_t B) {
+    int64_t c = B / 128 > 256 ? B / 128 : 256;
+    if (P.park_cap > 0) c = P.park_cap;
+    return c < B ? c : B;
+}
+
+struct Region {
+    size_t off = 0, bytes = 0;  // (bytes: what the region reserves)
+    size_t end() const { return off + bytes; }
+};
+// One phase's workspace: slot flags | counters | park indices | park ready flags | overflow list
+// | slots | park area.  Offsets from the phase's base.
+struct PhaseLayout {
+    // the 64 counters (int32_t, one 256-byte block)
+    enum Counter { PARK_COUNT, PARK_TAKEN, DONE, STARTED, OVF_COUNT, OVF_TAKEN, N_COUNTERS = 64 };
+    int64_t B = 0, nslots = 0, park_cap = 0;
+    int nxcc = 0;
+    size_t elem = 0;         // bytes of the solver's arithmetic type
+    int64_t slot_elems = 0;  // a slot: WideLayout::spill() in whole 128-byte lines
+    int64_t park_stride = 0;  // a park entry: WideLayout::park() in whole 128-byte lines
+    Region flags, counters, park_idx, park_ready, ovf, slots, park;
+    size_t total = 0;
+    // the overflow list: one index per problem (only where the park area can overflow)
+    bool has_ovf() const { return park_cap < B; }
+
+    PhaseLayout() = default;
+    PhaseLayout(const IpmParams& P, int64_t B_, int64_t budget, int nxcc_)
+        : B(B_), nslots(slot_count(budget, B_, nxcc_)), park_cap(wide_park_cap(P, B_)), nxcc(nxcc_), elem(elem_bytes(P)) {
+        const WideLayout L(P.N, P.filter_cap, P.model);
+        slot_elems = (int64_t)round_up((size_t)L.spill(), kLine / elem);
+        park_stride = (int64_t)round_up((size_t)L.park(), kLine / elem);
+        auto take = [this](size_t bytes) {
+            const Region r{total, bytes};
+            total += bytes;
+            return r;
+        };
+        flags = take(round_up((size_t)nslots * sizeof(int32_t), kWsAlign));
+        counters = take(N_COUNTERS * sizeof(int32_t));
+        park_idx = take(round_up((size_t)park_cap * sizeof(int64_t), kWsAlign));
+        park_ready = take(round_up((size_t)park_cap * sizeof(int32_t), kWsAlign));
+        ovf = take(has_ovf() ? round_up((size_t)B * sizeof(int64_t), kWsAlign) : 0);
+        slots = take((size_t)slot_elems * elem * (size_t)nslots);
+        park = take((size_t)park_stride * elem * (size_t)park_cap);
+    }
+};
+
+// A handle's whole workspace.  One phase at offset 0; the fp32 configuration: the larger of its
+// two phases' workspaces (the phases run one after the other), then the hand-over
+// (handoff_stride floats per problem: WideLayout::handoff in whole lines), the fp64 phase's
+// solve order (B indices, then its two counters -- k_cold_first), and the head's workspace.
+// budget(P, B): the slot budget of a phase, asked once per phase.
+struct SolveLayout {
+    bool two = false;
+    PhaseLayout first, second;  // second: the fp64 phase (the fp32 configuration)
+    size_t phases = 0;          // bytes at offset 0 that the phases share
+    Region handoff, order2, cnt2;
+    int64_t handoff_stride = 0;
+    int64_t head_n = 0;  // problems of the head the workspace has room for (head_count)
+    size_t head_off = 0;
+    PhaseLayout head;
+    size_t total = 0;
+
+    template <class Budget>
+    SolveLayout(const IpmParams& P, int64_t B, int nxcc, Budget&& budget)
+        : two(two_phase(P)), first(P, B, budget(P, B), nxcc), phases(first.total), total(first.total) {
+        if (!two) return;
+        const IpmParams Pr = fp64_params(P);
+        second = PhaseLayout(Pr, B, budget(Pr, B), nxcc);
+        phases = first.total > second.total ? first.total : second.total;
+        handoff_stride = (int64_t)round_up((size_t)WideLayout::handoff(P.N), kLine / sizeof(float));
+        handoff = Region{round_up(phases, kWsAlign), (size_t)handoff_stride * sizeof(float) * (size_t)B};
+        order2 = Region{handoff.end(), round_up((size_t)B, 64) * sizeof(int32_t)};
+        cnt2 = Region{order2.end(), 64 * sizeof(int32_t)};
+        head_off = total = round_up(cnt2.end(), kWsAlign);
+        head_n = head_count(B);
+        if (head_n > 0) {
+            const IpmParams Ph = head_params(P, head_n);
+            head = PhaseLayout(Ph, head_n, budget(Ph, head_n), nxcc);
+            total = head_off + head.total;
+        }
+    }
+};
+
+}  // namespace mpcg
+#endif

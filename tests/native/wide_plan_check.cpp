@@ -1,0 +1,217 @@
+// tests/native/wide_plan_check.cpp -- the launch plan of the wavefront solver
+// (mpc_ros_amd/csrc/wide_plan.h: instance choice and workspace layout) on the host; no GPU
+// runtime.  Checks the properties below (exit status 1 and a message at the first that fails),
+// then prints the chosen solve instance over the whole input space as JSON, run-length encoded
+// over the horizon: {"model<m>_precision<p>_<default|option>_B<B>": [[N from, N to, name], ...]}
+// ("": refused) -- tests/test_host_logic.py compares it with tests/golden/launch_plan.json.
+//
+//   g++ -std=c++20 -o wide_plan_check tests/native/wide_plan_check.cpp && ./wide_plan_check
+#include <cstdio>
+#include <cstdlib>
+#include <string>
+#include <vector>
+
+#include "../../mpc_ros_amd/csrc/wide_plan.h"
+
+using namespace mpcg;
+
+#define CHECK(c, ...)                                      \
+    do {                                                   \
+        if (!(c)) {                                        \
+            std::fprintf(stderr, "FAILED: %s -- ", #c);    \
+            std::fprintf(stderr, __VA_ARGS__);             \
+            std::fprintf(stderr, "\n");                    \
+            std::exit(1);                                  \
+        }                                                  \
+    } while (0)
+
+#define NAME7(g, M, S, T, NB, D, W) MPCG_SOLVE_NAME(M, S, T, NB, D, W),
+static const char* const kSolveNames[] = {MPCG_WIDE_SOLVE_INSTANCES(NAME7)};
+
+template <size_t n>
+static int index_of(const WideKey (&keys)[n], const WideKey& k) {
+    for (size_t i = 0; i < n; ++i)
+        if (keys[i] == k) return (int)i;
+    return -1;
+}
+
+static IpmParams params(int N, int model, int precision, bool option) {
+    IpmParams P{};
+    ipopt_default_options(P);
+    P.N = N;
+    P.model = model;
+    P.precision = precision;
+    P.lf = 0.5;
+    if (option) P.tol = 1e-7;  // (one non-default option)
+    return P;
+}
+
+// ------------------------------------------------------------------ the instance table
+static void check_instances() {
+    constexpr size_t ns = sizeof(kSolveKeys) / sizeof(WideKey), nr = sizeof(kResumeKeys) / sizeof(WideKey),
+                     nw = sizeof(kWarmKeys) / sizeof(WideKey);
+    bool used_s[ns] = {}, used_r[nr] = {}, used_w[nw] = {};
+    std::printf("{\n");
+    bool first = true;
+    for (int model = 0; model < 2; ++model)
+        for (int prec = 0; prec < 2; ++prec)
+            for (int opt = 0; opt < 2; ++opt)
+                for (long B : {1L, 4096L, 4097L}) {
+                    std::printf("%s  \"model%d_precision%d_%s_B%ld\": [", first ? "" : ",\n", model, prec,
+                                opt ? "option" : "default", B);
+                    first = false;
+                    std::string cur;
+                    int from = 1;
+                    bool f2 = true;
+                    for (int N = 1; N <= 129; ++N) {
+                        std::string name = "END";
+                        if (N <= 128) {
+                            const IpmParams P = params(N, model, prec, opt);
+                            const WideKey k = solve_key(P, B);
+                            const bool refused = prec == 1 && model == 1;  // (fp32: the differential drive)
+                            CHECK(k.ok() == !refused, "model %d precision %d N %d", model, prec, N);
+                            name = "";
+                            if (k.ok()) {
+                                const int i = index_of(kSolveKeys, k);
+                                CHECK(i >= 0, "solve key of model %d precision %d N %d option %d B %ld not in the list",
+                                      model, prec, N, opt, B);
+                                used_s[i] = true;
+                                name = kSolveNames[i];
+                                const int r = index_of(kResumeKeys, resume_key(P));
+                                CHECK(r >= 0, "resume key of model %d precision %d N %d", model, prec, N);
+                                used_r[r] = true;
+                                if (prec == 1) {
+                                    const int w = index_of(kWarmKeys, warm_key(fp64_params(P)));
+                                    CHECK(w >= 0, "warm key of N %d", N);
+                                    used_w[w] = true;
+                                }
+                            }
+                        }
+                        if (N == 1) cur = name;
+                        if (name != cur) {
+                            std::printf("%s[%d, %d, \"%s\"]", f2 ? "" : ", ", from, N - 1, cur.c_str());
+                            f2 = false;
+                            cur = name;
+                            from = N;
+                        }
+                    }
+                    std::printf("]");
+                }
+    std::printf("\n}\n");
+    // no dead instance
+    for (size_t i = 0; i < ns; ++i) CHECK(used_s[i], "solve instance %s is never chosen", kSolveNames[i]);
+    for (size_t i = 0; i < nr; ++i) CHECK(used_r[i], "resume instance %zu is never chosen", i);
+    for (size_t i = 0; i < nw; ++i) CHECK(used_w[i], "warm instance %zu is never chosen", i);
+    // refusals: more than 128 stages
+    CHECK(!solve_key(params(129, 0, 0, false), 1).ok() && !resume_key(params(129, 0, 0, false)).ok() &&
+              !warm_key(params(129, 0, 0, false)).ok(),
+          "N = 129");
+}
+
+// ------------------------------------------------------------------ the workspace layout
+static void check_phase(const PhaseLayout& W, const IpmParams& P, int64_t B, int64_t budget, int nxcc, const char* what) {
+    const WideLayout L(P.N, P.filter_cap, P.model);
+    const size_t eb = P.precision == 1 ? 4 : 8;
+    CHECK(W.B == B && W.nxcc == nxcc && W.elem == eb, "%s", what);
+    // slots: equal partitions per XCD, at least min(B, 32) each, at least min(budget, B) in all
+    CHECK(W.nslots % nxcc == 0 && W.nslots / nxcc >= (B < 32 ? B : 32) && W.nslots >= (budget < B ? budget : B) &&
+              W.nslots < (budget < B ? budget : B) + (B < 32 ? B : 32) * nxcc + nxcc,
+          "%s: nslots %lld", what, (long long)W.nslots);
+    const int64_t cap = P.park_cap > 0 ? P.park_cap : (B / 128 > 256 ? B / 128 : 256);
+    CHECK(W.park_cap == (cap < B ? cap : B), "%s: park_cap %lld", what, (long long)W.park_cap);
+    // whole 128-byte lines that hold the solver's own counts
+    CHECK(W.slot_elems >= L.spill() && (size_t)W.slot_elems * eb % 128 == 0 &&
+              (size_t)(W.slot_elems - L.spill()) * eb < 128,
+          "%s: slot_elems", what);
+    CHECK(W.park_stride >= L.park() && (size_t)W.park_stride * eb % 128 == 0 &&
+              (size_t)(W.park_stride - L.park()) * eb < 128,
+          "%s: park_stride", what);
+    // the regions in the stated order, each from a 256-byte boundary, none overlapping the next
+    const Region* r[] = {&W.flags, &W.counters, &W.park_idx, &W.park_ready, &W.ovf, &W.slots, &W.park};
+    CHECK(r[0]->off == 0, "%s", what);
+    for (int i = 0; i < 7; ++i) {
+        CHECK(r[i]->off % 256 == 0, "%s: region %d at %zu", what, i, r[i]->off);
+        if (i > 0) CHECK(r[i]->off == r[i - 1]->end(), "%s: region %d", what, i);
+    }
+    CHECK(W.total == W.park.end(), "%s: total", what);
+    // each holds what it is for
+    CHECK(W.flags.bytes >= (size_t)W.nslots * 4, "%s: flags", what);
+    CHECK(W.counters.bytes == 64 * 4 && PhaseLayout::OVF_TAKEN < PhaseLayout::N_COUNTERS, "%s: counters", what);
+    CHECK(W.park_idx.bytes >= (size_t)W.park_cap * 8 && W.park_ready.bytes >= (size_t)W.park_cap * 4, "%s: park flags", what);
+    CHECK(W.has_ovf() == (W.park_cap < B) && (W.ovf.bytes > 0) == W.has_ovf() &&
+              (!W.has_ovf() || W.ovf.bytes >= (size_t)B * 8),
+          "%s: overflow list", what);
+    CHECK(W.slots.bytes == (size_t)W.nslots * W.slot_elems * eb, "%s: slots", what);
+    CHECK(W.park.bytes == (size_t)W.park_cap * W.park_stride * eb, "%s: park area", what);
+}
+
+static int check_layouts() {
+    int cases = 0;
+    for (int N : {1, 20, 32, 33, 64, 65, 128})
+        for (int model : {0, 1})
+            for (int prec : {0, 1, 2})  // (2: fp32 with no_resto)
+                for (int64_t B : {1, 2, 31, 33, 2048, 2049, 65536})
+                    for (int64_t pcap : {(int64_t)0, (int64_t)1, B})
+                        for (int v : {0, 1}) {
+                            // (the fallback budget on 8 XCDs; a count that 4 XCDs do not divide)
+                            const int64_t budget = v == 0 ? 4096 : 1003;
+                            const int nxcc = v == 0 ? 8 : 4;
+                            IpmParams P = params(N, model, prec ? 1 : 0, false);
+                            P.no_resto = prec == 2;
+                            P.park_cap = (int)pcap;
+                            int asked = 0;
+                            const SolveLayout W(P, B, nxcc, [&](const IpmParams&, int64_t) {
+                                ++asked;
+                                return budget;
+                            });
+                            char what[128];
+                            std::snprintf(what, sizeof what, "N %d model %d precision %d B %lld park_cap %lld nxcc %d", N,
+                                          model, prec, (long long)B, (long long)pcap, nxcc);
+                            ++cases;
+                            check_phase(W.first, P, B, budget, nxcc, what);
+                            if (prec != 1) {  // one phase at offset 0
+                                CHECK(!W.two && W.total == W.first.total && W.head_n == 0 && asked == 1, "%s", what);
+                                continue;
+                            }
+                            const IpmParams Pr = fp64_params(P);
+                            check_phase(W.second, Pr, B, budget, nxcc, what);
+                            CHECK(W.two && W.phases == (W.first.total > W.second.total ? W.first.total : W.second.total),
+                                  "%s: phases", what);
+                            // the hand-over after the phases, whole lines that hold the solver's count
+                            CHECK(W.handoff.off % 256 == 0 && W.handoff.off >= W.phases, "%s: hand-over", what);
+                            CHECK(W.handoff_stride >= WideLayout::handoff(N) && W.handoff_stride % 32 == 0 &&
+                                      W.handoff_stride - WideLayout::handoff(N) < 32 &&
+                                      W.handoff.bytes == (size_t)W.handoff_stride * 4 * (size_t)B,
+                                  "%s: hand-over stride", what);
+                            // the fp64 phase's order, then its two counters in the space reserved for them
+                            CHECK(W.order2.off == W.handoff.end() && W.order2.off % 4 == 0 &&
+                                      W.order2.bytes >= (size_t)B * 4,
+                                  "%s: order", what);
+                            CHECK(W.cnt2.off == W.order2.end() && W.cnt2.bytes >= 2 * 4 && W.cnt2.end() <= W.head_off,
+                                  "%s: order counters", what);
+                            CHECK(W.head_off % 256 == 0, "%s: head offset", what);
+                            // the head: exactly beyond 2048 problems (ordered batches)
+                            CHECK((W.head_n > 0) == (B > 2048) && (W.head.total > 0) == (B > 2048) &&
+                                      W.total == W.head_off + W.head.total && asked == (B > 2048 ? 3 : 2),
+                                  "%s: head", what);
+                            if (W.head_n > 0) {
+                                CHECK(W.head_n == B / 1024, "%s: head count", what);
+                                const IpmParams Ph = head_params(P, W.head_n);
+                                check_phase(W.head, Ph, W.head_n, budget, nxcc, what);
+                                CHECK(!W.head.has_ovf(), "%s: a park entry per head problem", what);
+                                // (the phases beside a head cover B - K problems, in the space reserved for B)
+                                const int64_t Bm = B - W.head_n;
+                                CHECK(PhaseLayout(P, Bm, budget, nxcc).total <= W.phases &&
+                                          PhaseLayout(Pr, Bm, budget, nxcc).total <= W.phases,
+                                      "%s: the phases beside the head", what);
+                            }
+                        }
+    return cases;
+}
+
+int main() {
+    check_instances();
+    const int cases = check_layouts();
+    std::fprintf(stderr, "wide_plan_check: %d layouts ok\n", cases);
+    return 0;
+}

@@ -206,6 +206,33 @@ def test_workspace_bytes(libmpcg):
     assert libmpcg.mpcg_last_solve_order(None) == 0
 
 
+def test_workspace_bytes_match_the_record(libmpcg):
+    """mpcg_workspace_bytes over horizon classes x models x {fp64, fp32, fp32 without
+    restoration} x batch sizes equals what the library returned before the workspace layout
+    became one value (wide_plan.h SolveLayout): tests/golden/launch_plan.json, recorded without
+    a GPU (slot budget 4096, 8 XCDs).  With a GPU the slot budget is the device's occupancy,
+    which every row of at most 33 problems stays below on any device: those rows are compared
+    there, all 294 without one."""
+    import json
+
+    import torch
+
+    from mpc_ros_amd import _lib
+
+    with open(os.path.join(ROOT, "tests", "golden", "launch_plan.json")) as f:
+        rows = json.load(f)["workspace_bytes"]
+    assert len(rows) == 7 * 2 * 3 * 7
+    if torch.cuda.is_available():
+        rows = [r for r in rows if r[4] <= 33]
+    for steps, model, precision, no_resto, B, want in rows:
+        p = _lib.MpcgParams()
+        libmpcg.mpcg_params_plugin_default(C.byref(p))
+        p.steps, p.model, p.precision, p.no_restoration = steps, model, precision, no_resto
+        if model == 1:
+            p.wheelbase = 0.5
+        assert libmpcg.mpcg_workspace_bytes(C.byref(p), B) == want, (steps, model, precision, no_resto, B)
+
+
 def test_create_without_gpu_fails_loudly(libmpcg):
     import torch
 

@@ -95,7 +95,7 @@ def test_build_reads_kernel_resource_remarks():
 
 def test_parallel_build_units_cover_every_instance_group():
     """The parallel build compiles mpcg_wide_inst.hip once per group: the groups it names are
-    exactly the groups of the instance lists in mpcg_wide_kern.h (a group without a unit would
+    exactly the groups of the instance lists in wide_plan.h (a group without a unit would
     leave its kernels undefined at link time; a unit without instances is wasted), and every
     solve instance's (model, split, blocks) has an fp64 resume instance (its parked problems, and
     the fp32 solver's escalations)."""
@@ -103,7 +103,7 @@ def test_parallel_build_units_cover_every_instance_group():
 
     from mpc_ros_amd import build
 
-    text = open(os.path.join(build.CSRC, "mpcg_wide_kern.h")).read()
+    text = open(os.path.join(build.CSRC, "wide_plan.h")).read()
     solve = re.findall(r"X\((\d+), (\d), (true|false), (double|float), (\d), (true|false), (\d)\)", text)
     resume = re.findall(r"X\((\d+), (\d), (true|false), (double|float), (\d)\)", text)
     assert solve and resume
@@ -118,3 +118,34 @@ def test_parallel_build_units_cover_every_instance_group():
     # every source of the library is compiled exactly once besides the instance groups
     others = [u[0] for u in build.compile_units() if u[0] != build.INST]
     assert sorted(others) == sorted(s for s in build.SOURCES if s != build.INST)
+
+
+def test_launch_plan_native_check(tmp_path):
+    """tests/native/wide_plan_check.cpp (mpc_ros_amd/csrc/wide_plan.h on the host, no GPU
+    runtime): every chosen solve / resume / warm key is an instance the library carries and
+    every instance is chosen by some input; the workspace layout's regions are in order, aligned
+    and disjoint for every horizon class, precision, park capacity and batch size.  The solve
+    instance it chooses over model x precision x N = 1..128 x default / non-default options x
+    B in {1, 4096, 4097} equals the recorded choice of the dispatcher before the plan was a
+    header (tests/golden/launch_plan.json), which holds the names the GPU tests pin."""
+    import json
+    import re
+    import subprocess
+
+    from conftest import ROOT as root
+
+    exe = str(tmp_path / "wide_plan_check")
+    subprocess.check_call(["g++", "-O1", "-std=c++20", "-w", "-o", exe,
+                           os.path.join(root, "tests", "native", "wide_plan_check.cpp")])
+    r = subprocess.run([exe], capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr
+    with open(os.path.join(root, "tests", "golden", "launch_plan.json")) as f:
+        want = json.load(f)["instance_choice"]
+    got = json.loads(r.stdout)
+    assert len(want) == 24 and got == want
+    names = {row[2] for rows in want.values() for row in rows}
+    pinned = set()
+    for mod in ("test_gpu_options.py", "test_gpu_headline.py"):
+        text = open(os.path.join(root, "tests", mod)).read()
+        pinned |= set(re.findall(r'"(k_solve_wide<[^"]*>)"', text))
+    assert len(pinned) >= 3 and pinned <= names, pinned - names
