@@ -22,7 +22,7 @@ Fixtures (data only -- inputs and expected outputs):
                      (found by scanning with the oracle's diagnostics), the problems the
                      round-1 advisor named for the bounded filter (16101, 1887), and the
                      max_cpu_time iteration budget forced low; per problem the parameter
-                     set (N20 / N40 / bicycle), the oracle's diagnostics and results
+                     set (N20 / N40 / N65 / bicycle), the oracle's diagnostics and results
 
 All solves use the reference's options (oracle.pyoracle.ref_opts: Ipopt 3.12 defaults,
 max_cpu_time 0.5 s as its iteration budget).
@@ -97,8 +97,10 @@ def cppad_derivs():
 def solve_set(P, st, cf, opts=None):
     r = O.mpc_solve_batch(P, st, cf, opts=opts or O.ref_opts(int(P["STEPS"])), nthreads=os.cpu_count() or 8,
                           diag=True)
+    # (the fixtures keep diag's first five columns; the oracle's later ones, the slack margins, are
+    # checked on a live solve by tests/test_oracle.py)
     return dict(state=st, coeffs=cf, u0=r["u0"], traj=r["traj"], obj=r["obj"], status=r["status"],
-                iters=r["iters"], diag=r["diag"], params=np.array([P[k] for k in params.KEYS]))
+                iters=r["iters"], diag=np.ascontiguousarray(r["diag"][:, :5]), params=np.array([P[k] for k in params.KEYS]))
 
 
 def infinity_set():
@@ -173,14 +175,17 @@ FEATURE_SETS = {
     # N40: watchdog (88: six activations, 460, 842, 2012, 2094), soft restoration (422, 429,
     # 1431), restoration phase (69, 1167, 1204, 2956, 3441)
     "N40": (dict(PLUGIN, STEPS=40), [88, 460, 842, 2012, 2094, 422, 429, 1431, 69, 1167, 1204, 2956, 3441]),
-    # bicycle N25: watchdog (3308), soft restoration (1292), corrections (18, 23)
-    "bicycle": (BICYCLE, [3308, 1292, 18, 23]),
+    # bicycle N25: watchdog (3308), soft restoration (1292), corrections (18, 23), restoration
+    # phase (4330: 120 iterations, 4720)
+    "bicycle": (BICYCLE, [3308, 1292, 18, 23, 4330, 4720]),
     # the feasibility-restoration phase (round 3, found by scanning problems 0..131071 at
     # N = 20 and 0..32767 at N = 40 with the oracle's diagnostics): every problem of those
     # ranges on which Ipopt enters it
     "resto_N20": (PLUGIN, [1443, 40852, 74511, 84582]),
     "resto_N40": (dict(PLUGIN, STEPS=40), [69, 1167, 1204, 2956, 3441, 4626, 8420, 9871, 18581, 18819, 19148,
                                             19304, 23287, 25150, 25384, 28303, 30285, 31014, 31746]),
+    # the restoration phase at the smallest shape of two stage blocks per wavefront
+    "resto_N65": (dict(PLUGIN, STEPS=65), [1581]),
 }
 
 

@@ -137,15 +137,20 @@ def test_wide_core_filter_beyond_lds(wide_harness, features_golden):
         assert (r["n_fover"] == 0).all()
 
 
-@pytest.mark.parametrize("name", ["resto_N20", "resto_N40"])
+@pytest.mark.parametrize("name", ["resto_N20", "resto_N40", "resto_N65", "bicycle"])
 def test_wide_core_restoration_phase(wide_harness, features_golden, name):
     """Ipopt's feasibility-restoration phase (RestoIpoptNLP, one to three restoration
     iterations, then back to the original problem): same statuses, iteration counts and
     values as the oracle (tests/golden/ipopt_features.npz resto_* sets, every problem of the
-    scanned ranges that enters it; the GPU test runs all of them)."""
+    scanned ranges that enters it; the GPU test runs all of them).  resto_N65 and the bicycle
+    set's two restoring rows run the restoration solver of two stage blocks and of the bicycle
+    model."""
     g = features_golden[name]
-    rows = {"resto_N20": [0, 1, 3], "resto_N40": [2, 3, 11]}[name]
-    sub = subset(g, rows)
+    rows = {"resto_N20": [0, 1, 3], "resto_N40": [2, 3, 11], "resto_N65": [0]}.get(name)
+    if name == "bicycle":  # (the set's other rows never restore: these two at every MPCG_HOST_FULL)
+        sub = {k: g[k][[4, 5]] for k in ("state", "coeffs", "u0", "traj", "obj", "status", "iters", "diag")}
+    else:
+        sub = subset(g, rows)
     assert (sub["diag"][:, 3] > 0).all()
     r = run_harness(wide_harness, g["P"], sub["state"], sub["coeffs"])
     # (N40 problem 19304: 217 iterations through two restoration phases; its trajectory

@@ -97,7 +97,7 @@ def test_variants_match_oracle(torch_cuda, variants_golden, name):
         assert np.abs(r["iters"] - g["iters"]).max() <= SMALL_BOUND_ITERS_SLACK
 
 
-@pytest.mark.parametrize("name", ["N20", "N40", "bicycle", "resto_N20", "resto_N40"])
+@pytest.mark.parametrize("name", ["N20", "N40", "bicycle", "resto_N20", "resto_N40", "resto_N65"])
 def test_ipopt_features_match_oracle(torch_cuda, features_golden, name):
     """Problems on which Ipopt's second-order corrections, watchdog, soft restoration and
     feasibility-restoration phase act (tests/golden/ipopt_features.npz; the resto_* sets:

@@ -202,7 +202,12 @@ def test_oracle_ipopt_mechanisms_fire_and_reproduce(oracle, features_golden):
         for b in np.where(g["diag"][:, 3] > 0)[0][:3]:
             full = oracle.mpc_solve(P, g["state"][b], g["coeffs"][b], opts=oracle.ref_opts(int(P["STEPS"])), full=True)
             res = oracle.mpc_kkt_residual(P, g["state"][b], g["coeffs"][b], full["x"])
-            assert res["primal"] < 1e-8 and res["dual"] < 1e-5
+            # (the unscaled dual residual: 1e-5 on the N20 / N40 rows; Ipopt itself tests the
+            # scaled one against tol and the unscaled one against dual_inf_tol only, and on the
+            # bicycle's restoring row 4330 the oracle ends at 1.9e-5 -- as on other restoring
+            # rows of the resto_* sets, up to 0.16 on resto_N40's 25150)
+            dual_max = oracle.ref_opts(int(P["STEPS"])).dual_inf_tol if name == "bicycle" else 1e-5
+            assert res["primal"] < 1e-8 and res["dual"] < dual_max
     assert seen.all(), seen
 
 
@@ -249,7 +254,7 @@ def test_iterative_refinement_changes_no_fixture_row(oracle, infinity_golden, fe
     device's reduced restoration solve is not that accurate and refines every restoration step
     (wide_core.h refine_resto; tests/test_core_host.py SMALL_BOUND_ITERS_EXACT)."""
     sets = [("infinity", infinity_golden, 20, slice(0, 96))]
-    for name in ("N20", "N40", "bicycle", "resto_N20", "resto_N40"):
+    for name in ("N20", "N40", "bicycle", "resto_N20", "resto_N40", "resto_N65"):
         g = features_golden[name]
         sets.append((name, g, int(g["P"]["STEPS"]), slice(None)))
     for name, g, N, sl in sets:
@@ -274,7 +279,7 @@ def test_unrestated_ipopt_paths_never_reached(oracle, infinity_golden, features_
       restoration problem's line search fails, which is where the oracle (and the device) return
       RESTORATION_FAILURE (9): no row ends with 9."""
     sets = [("infinity", infinity_golden, None)]
-    for name in ("N20", "N40", "bicycle", "resto_N20", "resto_N40"):
+    for name in ("N20", "N40", "bicycle", "resto_N20", "resto_N40", "resto_N65"):
         sets.append((name, features_golden[name], None))
     for name in ("class_defaults", "no_rate", "rate_w", "N40", "N3", "small_bound", "N80", "N100"):
         sets.append((name, variants_golden[name], None))
