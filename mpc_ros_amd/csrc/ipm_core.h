@@ -81,54 +81,52 @@ struct IpmParams {
 };
 
 // The Ipopt 3.12 options the reference leaves at their defaults (mpc_planner.cpp:356-368:
-// only print_level, the derivative mode and max_cpu_time are set), as mpcg_api.cpp's
-// ipopt_defaults fills them.  A kernel instance for exactly these values compiles them as
-// constants (fewer wave-uniform values held through the solve); launch_wide_solve takes
-// it only when every field below equals the handle's option.
+// only print_level, the derivative mode and max_cpu_time are set): the one list of them.
+// mpcg_api.cpp fills mpcg_params' defaults and converts mpcg_params to IpmParams through it,
+// the host emulation (tests/native/wide_host_check.cpp) reads its options by the names in it.
+// X(type, IpmParams field, mpcg_params field = Ipopt's option name, Ipopt 3.12 default)
+#define MPCG_IPOPT_OPTIONS(X)                                                                  \
+    X(double, tol,                        tol,                                 1e-8)           \
+    X(double, bound_relax_factor,         bound_relax_factor,                  1e-8)           \
+    X(double, mu_init,                    mu_init,                             0.1)            \
+    X(int,    max_iter,                   max_iter,                            3000)           \
+    X(int,    filter_cap,                 filter_cap,                          64)             \
+    X(double, acceptable_tol,             acceptable_tol,                      1e-6)           \
+    X(int,    acceptable_iter,            acceptable_iter,                     15)             \
+    X(double, acceptable_dual_inf_tol,    acceptable_dual_inf_tol,             1e10)           \
+    X(double, acceptable_constr_viol_tol, acceptable_constr_viol_tol,          1e-2)           \
+    X(double, acceptable_compl_inf_tol,   acceptable_compl_inf_tol,            1e-2)           \
+    X(double, acceptable_obj_change_tol,  acceptable_obj_change_tol,           1e20)           \
+    X(int,    max_soc,                    max_soc,                             4)              \
+    X(double, kappa_soc,                  kappa_soc,                           0.99)           \
+    X(int,    watchdog_trigger,           watchdog_shortened_iter_trigger,     10)             \
+    X(int,    watchdog_trial_max,         watchdog_trial_iter_max,             3)              \
+    X(double, soft_resto_factor,          soft_resto_pderror_reduction_factor, 0.9999)         \
+    X(int,    max_soft_resto_iters,       max_soft_resto_iters,                10)             \
+    X(double, obj_max_inc,                obj_max_inc,                         5.0)            \
+    X(int,    max_filter_resets,          max_filter_resets,                   5)              \
+    X(int,    filter_reset_trigger,       filter_reset_trigger,                5)              \
+    X(double, tiny_step_tol,              tiny_step_tol,     10.0 * 2.220446049250313e-16)     \
+    X(double, tiny_step_y_tol,            tiny_step_y_tol,                     1e-2)           \
+    X(double, dual_inf_tol,               dual_inf_tol,                        1.0)            \
+    X(double, constr_viol_tol,            constr_viol_tol,                     1e-4)           \
+    X(double, compl_inf_tol,              compl_inf_tol,                       1e-4)           \
+    X(int,    no_resto,                   no_restoration,                      0)
+
+// A kernel instance for exactly the list's defaults compiles them as constants (fewer
+// wave-uniform values held through the solve); launch_wide_solve takes it only when every
+// option of the list equals the handle's.
 MPCG_HD void ipopt_default_options(IpmParams& q) {
-    q.no_resto = 0;
-    q.tol = 1e-8;
-    q.bound_relax_factor = 1e-8;
-    q.mu_init = 0.1;
-    q.max_iter = 3000;
-    q.filter_cap = 64;
-    q.acceptable_tol = 1e-6;
-    q.acceptable_iter = 15;
-    q.acceptable_dual_inf_tol = 1e10;
-    q.acceptable_constr_viol_tol = 1e-2;
-    q.acceptable_compl_inf_tol = 1e-2;
-    q.acceptable_obj_change_tol = 1e20;
-    q.max_soc = 4;
-    q.kappa_soc = 0.99;
-    q.watchdog_trigger = 10;
-    q.watchdog_trial_max = 3;
-    q.soft_resto_factor = 0.9999;
-    q.max_soft_resto_iters = 10;
-    q.obj_max_inc = 5.0;
-    q.max_filter_resets = 5;
-    q.filter_reset_trigger = 5;
-    q.tiny_step_tol = 10.0 * 2.220446049250313e-16;
-    q.tiny_step_y_tol = 1e-2;
-    q.dual_inf_tol = 1.0;
-    q.constr_viol_tol = 1e-4;
-    q.compl_inf_tol = 1e-4;
+#define MPCG_OPT_SET(type, field, name, dflt) q.field = dflt;
+    MPCG_IPOPT_OPTIONS(MPCG_OPT_SET)
+#undef MPCG_OPT_SET
 }
 inline bool ipopt_options_are_default(const IpmParams& p) {
     IpmParams q = p;
     ipopt_default_options(q);
-    return p.tol == q.tol && p.bound_relax_factor == q.bound_relax_factor && p.mu_init == q.mu_init &&
-           p.max_iter == q.max_iter && p.filter_cap == q.filter_cap && p.acceptable_tol == q.acceptable_tol &&
-           p.acceptable_iter == q.acceptable_iter && p.acceptable_dual_inf_tol == q.acceptable_dual_inf_tol &&
-           p.acceptable_constr_viol_tol == q.acceptable_constr_viol_tol &&
-           p.acceptable_compl_inf_tol == q.acceptable_compl_inf_tol &&
-           p.acceptable_obj_change_tol == q.acceptable_obj_change_tol && p.max_soc == q.max_soc &&
-           p.kappa_soc == q.kappa_soc && p.watchdog_trigger == q.watchdog_trigger &&
-           p.watchdog_trial_max == q.watchdog_trial_max && p.soft_resto_factor == q.soft_resto_factor &&
-           p.max_soft_resto_iters == q.max_soft_resto_iters && p.obj_max_inc == q.obj_max_inc &&
-           p.max_filter_resets == q.max_filter_resets && p.filter_reset_trigger == q.filter_reset_trigger &&
-           p.tiny_step_tol == q.tiny_step_tol && p.tiny_step_y_tol == q.tiny_step_y_tol &&
-           p.dual_inf_tol == q.dual_inf_tol && p.constr_viol_tol == q.constr_viol_tol &&
-           p.compl_inf_tol == q.compl_inf_tol && p.no_resto == q.no_resto;
+#define MPCG_OPT_EQ(type, field, name, dflt) && p.field == q.field
+    return true MPCG_IPOPT_OPTIONS(MPCG_OPT_EQ);
+#undef MPCG_OPT_EQ
 }
 
 // Status numbering of CppAD::ipopt::solve_result::status_type

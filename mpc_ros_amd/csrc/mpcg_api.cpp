@@ -86,35 +86,14 @@ const char* mpcg_build_id(void) {
 }
 const char* mpcg_last_error(void) { return g_err.c_str(); }
 
+// (the Ipopt options: ipm_core.h MPCG_IPOPT_OPTIONS)
 static void ipopt_defaults(mpcg_params* p) {
-    p->tol = 1e-8;
-    p->max_iter = 3000;
-    p->filter_cap = 64;
-    p->bound_relax_factor = 1e-8;
-    p->mu_init = 0.1;
+#define MPCG_OPT_DEFAULT(type, field, name, dflt) p->name = dflt;
+    MPCG_IPOPT_OPTIONS(MPCG_OPT_DEFAULT)
+#undef MPCG_OPT_DEFAULT
     p->wheelbase = 0.5;
     p->model = 0;
     p->max_cpu_time = 0.5;  // mpc_planner.cpp:368
-    p->acceptable_tol = 1e-6;
-    p->acceptable_dual_inf_tol = 1e10;
-    p->acceptable_constr_viol_tol = 1e-2;
-    p->acceptable_compl_inf_tol = 1e-2;
-    p->acceptable_obj_change_tol = 1e20;
-    p->kappa_soc = 0.99;
-    p->soft_resto_pderror_reduction_factor = 0.9999;
-    p->obj_max_inc = 5.0;
-    p->tiny_step_tol = 10.0 * 2.220446049250313e-16;
-    p->tiny_step_y_tol = 1e-2;
-    p->dual_inf_tol = 1.0;
-    p->constr_viol_tol = 1e-4;
-    p->compl_inf_tol = 1e-4;
-    p->acceptable_iter = 15;
-    p->max_soc = 4;
-    p->watchdog_shortened_iter_trigger = 10;
-    p->watchdog_trial_iter_max = 3;
-    p->max_soft_resto_iters = 10;
-    p->max_filter_resets = 5;
-    p->filter_reset_trigger = 5;
 }
 
 // max_cpu_time as the iterations the reference's Solve affords in that time at horizon
@@ -249,36 +228,13 @@ static mpcg::IpmParams to_ipm(const mpcg_params& p) {
     q.max_w = p.max_angvel;
     q.max_a = p.max_throttle;
     q.bound = p.bound;
-    q.tol = p.tol;
-    q.bound_relax_factor = p.bound_relax_factor;
-    q.mu_init = p.mu_init;
-    q.max_iter = p.max_iter;
-    q.filter_cap = p.filter_cap;
     q.model = p.model;
     q.lf = p.wheelbase;
-    q.acceptable_tol = p.acceptable_tol;
-    q.acceptable_iter = p.acceptable_iter;
-    q.acceptable_dual_inf_tol = p.acceptable_dual_inf_tol;
-    q.acceptable_constr_viol_tol = p.acceptable_constr_viol_tol;
-    q.acceptable_compl_inf_tol = p.acceptable_compl_inf_tol;
-    q.acceptable_obj_change_tol = p.acceptable_obj_change_tol;
-    q.max_soc = p.max_soc;
-    q.kappa_soc = p.kappa_soc;
-    q.watchdog_trigger = p.watchdog_shortened_iter_trigger;
-    q.watchdog_trial_max = p.watchdog_trial_iter_max;
-    q.soft_resto_factor = p.soft_resto_pderror_reduction_factor;
-    q.max_soft_resto_iters = p.max_soft_resto_iters;
-    q.obj_max_inc = p.obj_max_inc;
-    q.max_filter_resets = p.max_filter_resets;
-    q.filter_reset_trigger = p.filter_reset_trigger;
-    q.tiny_step_tol = p.tiny_step_tol;
-    q.tiny_step_y_tol = p.tiny_step_y_tol;
-    q.dual_inf_tol = p.dual_inf_tol;
-    q.constr_viol_tol = p.constr_viol_tol;
-    q.compl_inf_tol = p.compl_inf_tol;
+#define MPCG_OPT_COPY(type, field, name, dflt) q.field = p.name;
+    MPCG_IPOPT_OPTIONS(MPCG_OPT_COPY)
+#undef MPCG_OPT_COPY
     q.cpu_iter_budget = cpu_iter_budget(p.max_cpu_time, p.steps);
     q.precision = p.precision;
-    q.no_resto = p.no_restoration;
     return q;
 }
 

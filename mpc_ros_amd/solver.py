@@ -13,9 +13,10 @@ import numpy as np
 from . import _lib
 from .params import PLUGIN_DEFAULTS
 
-# Ipopt options of the reference's solve (mpc_planner.cpp:356-368: max_cpu_time 0.5, the
-# rest Ipopt 3.12 defaults); any mpcg_params field can be overridden by keyword
-IPOPT_DEFAULTS = dict(tol=1e-8, max_iter=3000, filter_cap=64, bound_relax_factor=1e-8, mu_init=0.1, max_cpu_time=0.5)
+# The Ipopt options of the reference's solve (mpc_planner.cpp:356-368: max_cpu_time 0.5, the rest
+# Ipopt 3.12 defaults) are the library's defaults (mpcg_params_default / _plugin_default); any
+# mpcg_params field can be overridden by keyword.
+
 # the fp32 configuration (precision 1, BASELINE configs[2]) runs two phases (mpcg_wide.hip):
 # (1) the fp32 solver on the whole batch with tolerances a float iterate can meet -- the scaled
 #     dual infeasibility of an fp32 iterate stalls near 1e-4 (multipliers ~1e3 times
@@ -33,6 +34,35 @@ IPOPT_DEFAULTS = dict(tol=1e-8, max_iter=3000, filter_cap=64, bound_relax_factor
 # alone and keeps its ending (status 9, 3 or 2 where it cannot finish).
 FP32_OPTIONS = dict(precision=1, tol=1e-3, compl_inf_tol=1e-2, tiny_step_tol=10 * 1.1920928955078125e-07,
                     acceptable_tol=1e-3, max_iter=300, no_restoration=0)
+
+
+def _params_struct(params, dtype, ipopt, base="plugin"):
+    """mpcg_params: the base's defaults ("plugin": PLUGIN_DEFAULTS' values, "class": MPC::MPC's),
+    the parameter map if any, then the keywords by field name (dtype "fp32": FP32_OPTIONS first)."""
+    if dtype == "fp32":
+        ipopt = dict(FP32_OPTIONS, **ipopt)
+    p = _lib.params_from_map(params if params is not None else {}, base)
+    for k, v in ipopt.items():
+        if not hasattr(p, k):
+            raise AttributeError(f"mpcg_params has no field {k!r}")
+        setattr(p, k, v)
+    return p
+
+
+def _host_batch(state, coeffs, N, want_traj=True, diag=False):
+    """The inputs as contiguous float64 arrays, the host output arrays of B solves by name, and
+    the pointers of both in the C-ABI's argument order."""
+    state = np.ascontiguousarray(state, dtype=np.float64)
+    coeffs = np.ascontiguousarray(coeffs, dtype=np.float64)
+    B = state.shape[0]
+    assert state.shape == (B, 6) and coeffs.shape == (B, 4), "state [B,6], coeffs [B,4]"
+    out = dict(u0=np.zeros((B, 2)), traj=np.zeros((B, 3, N)) if want_traj else None,
+               status=np.zeros(B, dtype=np.int32), obj=np.zeros(B), iters=np.zeros(B, dtype=np.int32))
+    if diag:
+        out["diag"] = np.zeros((B, 4), dtype=np.int32)
+    ptrs = [a.ctypes.data_as(C.POINTER(C.c_int32 if a.dtype == np.int32 else C.c_double)) if a is not None else None
+            for a in (state, coeffs, *out.values())]
+    return B, out, ptrs
 
 
 class BatchSolver:
@@ -73,13 +103,7 @@ class BatchSolver:
 
     # ------------------------------------------------------------ parameters
     def set_params(self, params: dict, base: str = "plugin", **ipopt):
-        p = _lib.params_from_map(params, base)
-        opts = dict(IPOPT_DEFAULTS)
-        opts.update(ipopt)
-        for k, v in opts.items():
-            if not hasattr(p, k):
-                raise AttributeError(f"mpcg_params has no field {k!r}")
-            setattr(p, k, v)
+        p = _params_struct(params, "fp64", ipopt, base)
         _lib.check(_lib.lib().mpcg_set_params(self._h, C.byref(p)), "mpcg_set_params")
         self.params = p
         self.N = p.steps
@@ -107,26 +131,11 @@ class BatchSolver:
 
     # ----------------------------------------------------------------- solve
     def solve(self, state: np.ndarray, coeffs: np.ndarray, want_traj: bool = True) -> dict:
-        state = np.ascontiguousarray(state, dtype=np.float64)
-        coeffs = np.ascontiguousarray(coeffs, dtype=np.float64)
-        B = state.shape[0]
-        assert state.shape == (B, 6) and coeffs.shape == (B, 4), "state [B,6], coeffs [B,4]"
-        N = self.N
-        u0 = np.zeros((B, 2))
-        traj = np.zeros((B, 3, N)) if want_traj else None
-        status = np.zeros(B, dtype=np.int32)
-        iters = np.zeros(B, dtype=np.int32)
-        obj = np.zeros(B)
-        diag = np.zeros((B, 4), dtype=np.int32)
-        dp = C.POINTER(C.c_double)
-        ip = C.POINTER(C.c_int32)
-        _lib.check(_lib.lib().mpcg_solve_ex(
-            self._h, B, state.ctypes.data_as(dp), coeffs.ctypes.data_as(dp), u0.ctypes.data_as(dp),
-            traj.ctypes.data_as(dp) if traj is not None else None, status.ctypes.data_as(ip),
-            obj.ctypes.data_as(dp), iters.ctypes.data_as(ip), diag.ctypes.data_as(ip)), "mpcg_solve_ex")
+        B, out, ptrs = _host_batch(state, coeffs, self.N, want_traj, diag=True)
+        _lib.check(_lib.lib().mpcg_solve_ex(self._h, B, *ptrs), "mpcg_solve_ex")
         # diag columns: restoration phases, filter entries dropped beyond its capacity, parked,
         # most filter entries held at once
-        return dict(u0=u0, traj=traj, status=status, obj=obj, iters=iters, diag=diag)
+        return out
 
     def solve_device(self, state, coeffs, u0, traj=None, status=None, obj=None, iters=None, stream=None, diag=None):
         """All arguments are torch tensors on this handle's GPU (float64 / int32, contiguous);
@@ -206,19 +215,6 @@ class BatchSolver:
             C.c_void_p(stream.cuda_stream)), "mpcg_track_device")
 
 
-def _params_struct(params, dtype, ipopt):
-    if dtype == "fp32":
-        ipopt = dict(FP32_OPTIONS, **ipopt)
-    p = _lib.params_from_map(params if params is not None else PLUGIN_DEFAULTS)
-    opts = dict(IPOPT_DEFAULTS)
-    opts.update(ipopt)
-    for k, v in opts.items():
-        if not hasattr(p, k):
-            raise AttributeError(f"mpcg_params has no field {k!r}")
-        setattr(p, k, v)
-    return p
-
-
 class MultiSolver:
     """mpcg_multi: a persistent multi-GPU context (communicator, per-GPU handles, streams and
     buffers for batches of up to B_max problems, created once); ``solve`` shards a host batch
@@ -235,23 +231,9 @@ class MultiSolver:
         self._h = h
 
     def solve(self, state, coeffs) -> dict:
-        state = np.ascontiguousarray(state, dtype=np.float64)
-        coeffs = np.ascontiguousarray(coeffs, dtype=np.float64)
-        B = state.shape[0]
-        assert state.shape == (B, 6) and coeffs.shape == (B, 4), "state [B,6], coeffs [B,4]"
-        N = self.N
-        u0 = np.zeros((B, 2))
-        traj = np.zeros((B, 3, N))
-        status = np.zeros(B, dtype=np.int32)
-        iters = np.zeros(B, dtype=np.int32)
-        obj = np.zeros(B)
-        dp = C.POINTER(C.c_double)
-        ip = C.POINTER(C.c_int32)
-        _lib.check(_lib.lib().mpcg_multi_solve(
-            self._h, B, state.ctypes.data_as(dp), coeffs.ctypes.data_as(dp), u0.ctypes.data_as(dp),
-            traj.ctypes.data_as(dp), status.ctypes.data_as(ip), obj.ctypes.data_as(dp), iters.ctypes.data_as(ip)),
-            "mpcg_multi_solve")
-        return dict(u0=u0, traj=traj, status=status, obj=obj, iters=iters)
+        B, out, ptrs = _host_batch(state, coeffs, self.N)
+        _lib.check(_lib.lib().mpcg_multi_solve(self._h, B, *ptrs), "mpcg_multi_solve")
+        return out
 
     def close(self):
         if getattr(self, "_h", None) is not None and self._h.value:
@@ -270,30 +252,8 @@ def solve_multi(devices, params: dict | None = None, state=None, coeffs=None, dt
     devices[0] by RCCL (include/mpcg.h).  Only ngpu = 1 has run on hardware (the GPU boxes
     this was developed on hold one MI355X); the shard and gather arithmetic for ngpu > 1 is
     unit-tested on the CPU (tests/test_abi.py)."""
-    state = np.ascontiguousarray(state, dtype=np.float64)
-    coeffs = np.ascontiguousarray(coeffs, dtype=np.float64)
-    B = state.shape[0]
-    assert state.shape == (B, 6) and coeffs.shape == (B, 4), "state [B,6], coeffs [B,4]"
-    if dtype == "fp32":
-        ipopt = dict(FP32_OPTIONS, **ipopt)
-    p = _lib.params_from_map(params if params is not None else PLUGIN_DEFAULTS)
-    opts = dict(IPOPT_DEFAULTS)
-    opts.update(ipopt)
-    for k, v in opts.items():
-        if not hasattr(p, k):
-            raise AttributeError(f"mpcg_params has no field {k!r}")
-        setattr(p, k, v)
-    N = p.steps
-    u0 = np.zeros((B, 2))
-    traj = np.zeros((B, 3, N))
-    status = np.zeros(B, dtype=np.int32)
-    iters = np.zeros(B, dtype=np.int32)
-    obj = np.zeros(B)
+    p = _params_struct(params, dtype, ipopt)
+    B, out, ptrs = _host_batch(state, coeffs, p.steps)
     dev = (C.c_int * len(devices))(*devices)
-    dp = C.POINTER(C.c_double)
-    ip = C.POINTER(C.c_int32)
-    _lib.check(_lib.lib().mpcg_solve_multi(
-        len(devices), dev, C.byref(p), B, state.ctypes.data_as(dp), coeffs.ctypes.data_as(dp), u0.ctypes.data_as(dp),
-        traj.ctypes.data_as(dp), status.ctypes.data_as(ip), obj.ctypes.data_as(dp), iters.ctypes.data_as(ip)),
-        "mpcg_solve_multi")
-    return dict(u0=u0, traj=traj, status=status, obj=obj, iters=iters)
+    _lib.check(_lib.lib().mpcg_solve_multi(len(devices), dev, C.byref(p), B, *ptrs), "mpcg_solve_multi")
+    return out

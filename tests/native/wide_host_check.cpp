@@ -12,11 +12,10 @@
 //
 // stdin:  N dt ref_cte ref_eth ref_v w_cte w_eth w_v w_w w_a w_dw w_da max_w max_a bound tol max_iter
 //         model lf
-//         acceptable_tol acceptable_iter acceptable_dual_inf_tol acceptable_constr_viol_tol
-//         acceptable_compl_inf_tol acceptable_obj_change_tol max_soc kappa_soc wd_trigger
-//         wd_trial_max soft_factor max_soft_iters obj_max_inc max_filter_resets
-//         filter_reset_trigger tiny_step_tol tiny_step_y_tol cpu_iter_budget filter_cap
-//         dual_inf_tol constr_viol_tol compl_inf_tol mu_init bound_relax_factor no_resto
+//         the Ipopt options, one "name value" line each under Ipopt's name (the third column of
+//         ipm_core.h's MPCG_IPOPT_OPTIONS) or cpu_iter_budget, in any order, closed by a line
+//         "end": an option left out keeps Ipopt's default (no iteration budget), an unknown
+//         name ends the run with exit status 2
 //         B, then B x (state[6], coeffs[4])
 // stdout: per problem: status iters obj u0[2] traj[3N] restoration-phases filter-overflows filter-peak
 #include <barrier>
@@ -25,6 +24,7 @@
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <memory>
 #include <string>
 #include <thread>
@@ -228,24 +228,27 @@ struct HostWave {
 
 int main() {
     mpcg::IpmParams P{};
+    mpcg::ipopt_default_options(P);
+    P.cpu_iter_budget = -1;
     if (std::scanf("%d %lf %lf %lf %lf %lf %lf %lf %lf %lf %lf %lf %lf %lf %lf %lf %d", &P.N, &P.dt, &P.ref_cte,
                    &P.ref_eth, &P.ref_v, &P.w_cte, &P.w_eth, &P.w_v, &P.w_w, &P.w_a, &P.w_dw, &P.w_da, &P.max_w,
                    &P.max_a, &P.bound, &P.tol, &P.max_iter) != 17)
         return 1;
-    P.filter_cap = 64;
-    P.model = 0;
-    P.lf = 0.5;
     if (std::scanf("%d %lf", &P.model, &P.lf) != 2) return 1;
-    if (std::scanf("%lf %d %lf %lf %lf %lf %d %lf %d %d %lf %d %lf %d %d %lf %lf %d %d", &P.acceptable_tol,
-                   &P.acceptable_iter, &P.acceptable_dual_inf_tol, &P.acceptable_constr_viol_tol,
-                   &P.acceptable_compl_inf_tol, &P.acceptable_obj_change_tol, &P.max_soc, &P.kappa_soc,
-                   &P.watchdog_trigger, &P.watchdog_trial_max, &P.soft_resto_factor, &P.max_soft_resto_iters,
-                   &P.obj_max_inc, &P.max_filter_resets, &P.filter_reset_trigger, &P.tiny_step_tol,
-                   &P.tiny_step_y_tol, &P.cpu_iter_budget, &P.filter_cap) != 19)
-        return 1;
-    if (std::scanf("%lf %lf %lf %lf %lf %d", &P.dual_inf_tol, &P.constr_viol_tol, &P.compl_inf_tol, &P.mu_init,
-                   &P.bound_relax_factor, &P.no_resto) != 6)
-        return 1;
+    for (char key[64];;) {
+        double v;
+        if (std::scanf("%63s", key) != 1) return 1;
+        if (!std::strcmp(key, "end")) break;
+        if (std::scanf("%lf", &v) != 1) return 1;
+        if (!std::strcmp(key, "cpu_iter_budget")) P.cpu_iter_budget = (int)v;
+#define OPT_BY_NAME(type, field, name, dflt) else if (!std::strcmp(key, #name)) P.field = (type)v;
+        MPCG_IPOPT_OPTIONS(OPT_BY_NAME)
+#undef OPT_BY_NAME
+        else {
+            std::fprintf(stderr, "unknown option %s\n", key);
+            return 2;
+        }
+    }
     long B;
     if (std::scanf("%ld", &B) != 1) return 1;
     const bool two_phase = std::getenv("MPCG_HOST_TWO_PHASE") && std::atoi(std::getenv("MPCG_HOST_TWO_PHASE")) != 0;

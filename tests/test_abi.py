@@ -38,11 +38,12 @@ def test_abi_version_and_struct_size(libmpcg):
     from mpc_ros_amd import _lib
 
     assert libmpcg.mpcg_abi_version() == _lib.ABI_VERSION == 2
-    # C struct layout: compile a tiny probe against the header and compare sizeof/offsets
-    src = ("#include <stdio.h>\n#include <stddef.h>\n#include \"mpcg.h\"\nint main(){printf(\"%zu %zu %zu %zu %zu %zu\","
-           "sizeof(mpcg_params),offsetof(mpcg_params,tol),offsetof(mpcg_params,filter_cap),"
-           "offsetof(mpcg_params,wheelbase),offsetof(mpcg_params,max_cpu_time),"
-           "offsetof(mpcg_params,filter_reset_trigger));}\n")
+    # C struct layout: compile a tiny probe against the header and compare sizeof and the offset
+    # of every field of the ctypes mirror
+    P = _lib.MpcgParams
+    names = [n for n, _ in P._fields_]
+    src = ("#include <stdio.h>\n#include <stddef.h>\n#include \"mpcg.h\"\nint main(){printf(\"%zu\",sizeof(mpcg_params));\n"
+           + "".join(f"printf(\" %zu\",offsetof(mpcg_params,{n}));\n" for n in names) + "}\n")
     import tempfile
 
     with tempfile.TemporaryDirectory() as d:
@@ -50,9 +51,25 @@ def test_abi_version_and_struct_size(libmpcg):
         subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), "-o", os.path.join(d, "p"),
                                os.path.join(d, "p.c")])
         got = [int(v) for v in subprocess.check_output([os.path.join(d, "p")]).split()]
-    P = _lib.MpcgParams
-    assert got == [C.sizeof(P), P.tol.offset, P.filter_cap.offset, P.wheelbase.offset, P.max_cpu_time.offset,
-                   P.filter_reset_trigger.offset]
+    assert len(names) == 45 and got == [C.sizeof(P)] + [getattr(P, n).offset for n in names]
+
+
+def test_option_defaults_equal_the_oracles(libmpcg, oracle):
+    """Every Ipopt option mpcg_params and the oracle's IpmOpts share by name has the oracle's
+    default (ora_ipm_default_opts: the independent restatement of Ipopt 3.12's) in both sets of
+    product defaults."""
+    from mpc_ros_amd import _lib
+
+    o = oracle.IpmOpts()
+    oracle.lib().ora_ipm_default_opts(C.byref(o))
+    common = [n for n, _ in _lib.MpcgParams._fields_ if n in dict(oracle.IpmOpts._fields_)]
+    assert len(common) == 24
+    for default in (libmpcg.mpcg_params_default, libmpcg.mpcg_params_plugin_default):
+        p = _lib.MpcgParams()
+        assert default(C.byref(p)) == 0
+        for n in common:
+            assert getattr(p, n) == getattr(o, n), n
+        assert p.no_restoration == (0 if o.restoration else 1)
 
 
 def test_build_id_is_the_source_hash(libmpcg):

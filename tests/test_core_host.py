@@ -29,16 +29,34 @@ def subset(g, rows):
     return {k: g[k][rows] for k in keys if k in g}
 
 
+# fields of the oracle's IpmOpts that are no option of the device core
+ORACLE_ONLY = ("honor_original_bounds", "print_level", "kkt_structured", "refine_steps")
+
+
 def opts_line(o, filter_cap=64) -> str:
-    """The harness's Ipopt-option lines from an oracle IpmOpts (same values both sides;
-    restoration = 0 is the core's no_resto = 1)."""
-    return (f"{o.acceptable_tol!r} {o.acceptable_iter} {o.acceptable_dual_inf_tol!r} {o.acceptable_constr_viol_tol!r} "
-            f"{o.acceptable_compl_inf_tol!r} {o.acceptable_obj_change_tol!r} {o.max_soc} {o.kappa_soc!r} "
-            f"{o.watchdog_shortened_iter_trigger} {o.watchdog_trial_iter_max} "
-            f"{o.soft_resto_pderror_reduction_factor!r} {o.max_soft_resto_iters} {o.obj_max_inc!r} "
-            f"{o.max_filter_resets} {o.filter_reset_trigger} {o.tiny_step_tol!r} {o.tiny_step_y_tol!r} "
-            f"{o.cpu_iter_budget} {int(filter_cap)}\n{o.dual_inf_tol!r} {o.constr_viol_tol!r} {o.compl_inf_tol!r} "
-            f"{o.mu_init!r} {o.bound_relax_factor!r} {0 if o.restoration else 1}")
+    """The harness's Ipopt-option lines from an oracle IpmOpts: every field under its own name
+    (same values both sides; restoration = 0 is the core's no_restoration = 1), closed by "end".
+    The harness refuses a name the core does not have."""
+    lines = [f"filter_cap {int(filter_cap)}"]
+    for name, _ in o._fields_:
+        if name in ORACLE_ONLY:
+            continue
+        if name == "restoration":
+            lines.append(f"no_restoration {0 if o.restoration else 1}")
+        else:
+            lines.append(f"{name} {getattr(o, name)!r}")
+    return "\n".join(lines + ["end"])
+
+
+def harness_stdin(P, state, coeffs, o, options) -> str:
+    """The harness's input: the two problem lines, the option lines, the problems."""
+    hdr = (f"{int(P['STEPS'])} {P['DT']!r} {P['REF_CTE']!r} {P['REF_ETHETA']!r} {P['REF_V']!r} {P['W_CTE']!r} "
+           f"{P['W_EPSI']!r} {P['W_V']!r} {P['W_ANGVEL']!r} {P['W_A']!r} {P['W_DANGVEL']!r} {P['W_DA']!r} "
+           f"{P['ANGVEL']!r} {P['MAXTHR']!r} {P['BOUND']!r} {o.tol!r} {o.max_iter}\n"
+           f"{int(P.get('MODEL', 0))} {float(P.get('LF', 0.5))!r}\n{options}\n{len(state)}\n")
+    body = "\n".join(" ".join(repr(float(v)) for v in np.concatenate([state[b], coeffs[b]]))
+                     for b in range(len(state)))
+    return hdr + body + "\n"
 
 
 def run_harness(exe, P, state, coeffs, opts=None, env=None, filter_cap=64):
@@ -46,14 +64,8 @@ def run_harness(exe, P, state, coeffs, opts=None, env=None, filter_cap=64):
 
     N = int(P["STEPS"])
     o = opts if opts is not None else O.ref_opts(N)
-    hdr = (f"{N} {P['DT']!r} {P['REF_CTE']!r} {P['REF_ETHETA']!r} {P['REF_V']!r} {P['W_CTE']!r} {P['W_EPSI']!r} "
-           f"{P['W_V']!r} {P['W_ANGVEL']!r} {P['W_A']!r} {P['W_DANGVEL']!r} {P['W_DA']!r} {P['ANGVEL']!r} "
-           f"{P['MAXTHR']!r} {P['BOUND']!r} {o.tol!r} {o.max_iter}\n{int(P.get('MODEL', 0))} {float(P.get('LF', 0.5))!r}\n"
-           f"{opts_line(o, filter_cap)}\n{len(state)}\n")
-    body = "\n".join(" ".join(repr(float(v)) for v in np.concatenate([state[b], coeffs[b]]))
-                     for b in range(len(state)))
-    out = subprocess.run([exe], input=hdr + body + "\n", capture_output=True, text=True, check=True,
-                         env=dict(os.environ, **(env or {}))).stdout
+    out = subprocess.run([exe], input=harness_stdin(P, state, coeffs, o, opts_line(o, filter_cap)),
+                         capture_output=True, text=True, check=True, env=dict(os.environ, **(env or {}))).stdout
     rows = np.array([r.split() for r in out.strip().split("\n")], dtype=np.float64)
     return dict(status=rows[:, 0].astype(int), iters=rows[:, 1].astype(int), obj=rows[:, 2], u0=rows[:, 3:5],
                 traj=rows[:, 5:5 + 3 * N].reshape(len(state), 3, N), n_resto=rows[:, 5 + 3 * N].astype(int),
@@ -106,6 +118,25 @@ def test_wide_core_matches_oracle_infinity_subset(wide_harness, infinity_golden)
     sub = {k: g[k][sel] for k in ("state", "coeffs", "u0", "traj", "obj", "status", "iters", "diag")}
     r = run_harness(wide_harness, params_from_array(g["params"]), sub["state"], sub["coeffs"])
     compare(r, sub, atol=1e-9)
+
+
+def test_harness_options_by_name(wide_harness, infinity_golden, oracle):
+    """The harness's option input: a name it does not know ends the run with a non-zero exit
+    status, and an option left out keeps Ipopt's default -- a block of "end" alone gives the
+    output of the full block of defaults."""
+    g = infinity_golden
+    P = params_from_array(g["params"])
+    o = oracle.ref_opts(int(P["STEPS"]))
+
+    def run(options):
+        return subprocess.run([wide_harness], input=harness_stdin(P, g["state"][:2], g["coeffs"][:2], o, options),
+                              capture_output=True, text=True)
+
+    full, bare = run(opts_line(o)), run("end")
+    assert full.returncode == 0 and bare.returncode == 0
+    assert len(full.stdout.splitlines()) == 2 and bare.stdout == full.stdout
+    bad = run("no_such_option 1\n" + opts_line(o))
+    assert bad.returncode != 0 and "no_such_option" in bad.stderr and bad.stdout == ""
 
 
 @pytest.mark.parametrize("name", ["N20", "N40", "bicycle"])

@@ -149,3 +149,29 @@ def test_launch_plan_native_check(tmp_path):
         text = open(os.path.join(root, "tests", mod)).read()
         pinned |= set(re.findall(r'"(k_solve_wide<[^"]*>)"', text))
     assert len(pinned) >= 3 and pinned <= names, pinned - names
+
+
+def test_params_struct_bytes(libmpcg):
+    """solver._params_struct adds nothing of its own to the library's defaults: without keywords
+    its struct is the bytes mpcg_params_plugin_default / mpcg_params_default write (the plugin's
+    are params.PLUGIN_DEFAULTS' values); "fp32" changes the fields of
+    FP32_OPTIONS and no other; a keyword that is no field raises."""
+    import ctypes as C
+
+    from mpc_ros_amd import _lib, solver
+
+    for base, default in (("plugin", libmpcg.mpcg_params_plugin_default), ("class", libmpcg.mpcg_params_default)):
+        want = _lib.MpcgParams()
+        assert default(C.byref(want)) == 0
+        assert bytes(solver._params_struct(None, "fp64", {}, base=base)) == bytes(want)
+    plugin = _lib.MpcgParams()
+    assert libmpcg.mpcg_params_plugin_default(C.byref(plugin)) == 0
+    assert bytes(solver._params_struct(None, "fp64", {})) == bytes(plugin)
+    assert bytes(solver._params_struct(params.PLUGIN_DEFAULTS, "fp64", {})) == bytes(plugin)
+    p32 = solver._params_struct(None, "fp32", {})
+    differ = {n for n, _ in _lib.MpcgParams._fields_ if getattr(p32, n) != getattr(plugin, n)}
+    # (no_restoration = 0 is FP32_OPTIONS' value and the default alike)
+    assert differ == set(solver.FP32_OPTIONS) - {"no_restoration"}
+    assert all(getattr(p32, k) == v for k, v in solver.FP32_OPTIONS.items())
+    with pytest.raises(AttributeError):
+        solver._params_struct(None, "fp64", {"no_such_option": 1})

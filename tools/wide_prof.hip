@@ -92,15 +92,10 @@ int main(int argc, char** argv) {
     mpcg::IpmParams P{};
     P.N = 20; P.dt = 0.1; P.ref_cte = 0; P.ref_eth = 0; P.ref_v = 1.0;
     P.w_cte = 1000; P.w_eth = 1000; P.w_v = 100; P.w_w = 100; P.w_a = 50; P.w_dw = 0; P.w_da = 10;
-    P.max_w = 1.0; P.max_a = 1.0; P.bound = 1000; P.tol = 1e-8; P.bound_relax_factor = 1e-8; P.mu_init = 0.1;
-    P.max_iter = 3000; P.filter_cap = 64; P.model = 0; P.lf = 0.5;
-    // Ipopt 3.12 defaults and the max_cpu_time budget at N = 20 (mpcg_api.cpp ipopt_defaults, cpu_iter_budget)
-    P.acceptable_tol = 1e-6; P.acceptable_iter = 15; P.acceptable_dual_inf_tol = 1e10;
-    P.acceptable_constr_viol_tol = 1e-2; P.acceptable_compl_inf_tol = 1e-2; P.acceptable_obj_change_tol = 1e20;
-    P.max_soc = 4; P.kappa_soc = 0.99; P.watchdog_trigger = 10; P.watchdog_trial_max = 3;
-    P.soft_resto_factor = 0.9999; P.max_soft_resto_iters = 10; P.obj_max_inc = 5; P.max_filter_resets = 5;
-    P.filter_reset_trigger = 5; P.tiny_step_tol = 10 * 2.220446049250313e-16; P.tiny_step_y_tol = 1e-2;
-    P.dual_inf_tol = 1; P.constr_viol_tol = 1e-4; P.compl_inf_tol = 1e-4; P.cpu_iter_budget = 1520; P.precision = 0;
+    P.max_w = 1.0; P.max_a = 1.0; P.bound = 1000; P.model = 0; P.lf = 0.5;
+    // Ipopt 3.12 defaults and the max_cpu_time budget at N = 20 (mpcg_api.cpp cpu_iter_budget)
+    mpcg::ipopt_default_options(P);
+    P.cpu_iter_budget = 1520; P.precision = 0;
     double *dst, *dcf;
     unsigned long long* dacc;
     int *dit, *dss;
