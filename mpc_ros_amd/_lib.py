@@ -80,6 +80,15 @@ SIGNATURES = {
     "mpcg_track_device": ([C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p], C.c_int),
     "mpcg_synchronize": ([C.c_void_p], C.c_int),
+    "mpcg_pparams_fill": ([_PP, C.c_int64, _dp], C.c_int),
+    "mpcg_pparams_check": ([_dp, C.c_int64, C.c_int32, C.POINTER(C.c_int64)], C.c_int),
+    "mpcg_solve_pp": ([C.c_void_p, C.c_int64, _dp, _dp, _dp, _dp, _dp, _ip, _dp, _ip, _ip], C.c_int),
+    "mpcg_solve_device_pp": ([C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                              C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p], C.c_int),
+    "mpcg_decelerate": ([C.c_double] * 6, C.c_double),
+    "mpcg_track_device_goal": ([C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                C.c_void_p, C.c_double, C.c_double, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                C.c_void_p], C.c_int),
     "mpcg_solve_multi": ([C.c_int, C.POINTER(C.c_int), _PP, C.c_int64, _dp, _dp, _dp, _dp, _ip, _dp, _ip], C.c_int),
     "mpcg_shard_range": ([C.c_int64, C.c_int, C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int64)], C.c_int),
     "mpcg_multi_gather_plan": ([C.c_int64, C.c_int32, C.c_int, C.c_int, C.c_void_p], C.c_int),
@@ -96,6 +105,8 @@ SIGNATURES = {
     "mpcg_synth_infinity_device": ([C.c_void_p, C.c_uint64, C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p,
                                     C.c_void_p, C.c_void_p], C.c_int),
 }
+
+PP_FIELDS = 16  # MPCG_PP_FIELDS: doubles per parameter row (their order: params.ROW_KEYS)
 
 STRATEGY = {"auto": 0, "lane": 1, "wave": 2}  # (LANE was removed in ABI 2: selecting it raises)
 ABI_VERSION = 2

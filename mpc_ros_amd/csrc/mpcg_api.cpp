@@ -12,6 +12,7 @@
 
 #include "mpcg.h"
 #include "mpcg_internal.h"
+#include "mpcg_pp.h"
 
 namespace {
 thread_local std::string g_err;
@@ -49,6 +50,9 @@ struct mpcg_handle {
     // mpcg_track_device intermediates: state [B][6] | coeffs [B][4] | u0 [B][2]
     double* d_trk = nullptr;
     size_t trk_bytes = 0;
+    // mpcg_track_device_goal: the robots' parameter rows [B][16]
+    double* d_rows = nullptr;
+    size_t rows_bytes = 0;
     // preprocessing scratch of plans longer than 64 waypoints
     double* d_pp = nullptr;
     size_t pp_bytes = 0;
@@ -298,6 +302,7 @@ void mpcg_destroy(mpcg_handle* h) {
     if (h->have_last) hipEventSynchronize(h->last_ev);
     if (h->d_io) hipFree(h->d_io);
     if (h->d_trk) hipFree(h->d_trk);
+    if (h->d_rows) hipFree(h->d_rows);
     if (h->d_pp) hipFree(h->d_pp);
     if (h->d_sched) hipFree(h->d_sched);
     if (h->d_spill) hipFree(h->d_spill);
@@ -417,15 +422,20 @@ int mpcg_solve_device(mpcg_handle* h, int64_t B, const double* d_state, const do
     return mpcg_solve_device_ex(h, B, d_state, d_coeffs, d_u0, d_traj, d_status, d_obj, d_iters, nullptr, stream);
 }
 
-int mpcg_solve_device_ex(mpcg_handle* h, int64_t B, const double* d_state, const double* d_coeffs, double* d_u0,
-                         double* d_traj, int32_t* d_status, double* d_obj, int32_t* d_iters, int32_t* d_diag,
-                         void* stream) {
+static const char kNoFp32Rows[] =
+    "precision 1 (fp32) takes no per-problem parameter rows: its fp64 phase and head have no per-problem instances";
+
+// the device solve; d_pparams: a parameter row per problem (mpcg_solve_device_pp) or null
+static int solve_device(mpcg_handle* h, int64_t B, const double* d_state, const double* d_coeffs,
+                        const double* d_pparams, double* d_u0, double* d_traj, int32_t* d_status, double* d_obj,
+                        int32_t* d_iters, int32_t* d_diag, void* stream) {
     if (!h) return fail(-1, "null handle");
     if (B < 0) return fail(-1, "negative batch");
     if (B == 0) return 0;
     if (!d_state || !d_coeffs || !d_u0) return fail(-1, "state, coeffs and u0 are required");
     int rc = mpcg_params_check(&h->params);
     if (rc) return rc;
+    if (d_pparams && h->params.precision != 0) return fail(-1, kNoFp32Rows);
     hipError_t e = hipSetDevice(h->device);
     if (e != hipSuccess) return hip_fail(e, "hipSetDevice");
     hipStream_t s = (hipStream_t)stream;  // NULL = the null stream, as in HIP
@@ -455,10 +465,23 @@ int mpcg_solve_device_ex(mpcg_handle* h, int64_t B, const double* d_state, const
     ws.ev_join = h->ev_join;
     ws.ev_join2 = h->ev_join2;
     e = mpcg::launch_wide_solve(P, B, d_state, d_coeffs, d_u0, d_traj, d_status, d_obj, d_iters, d_diag, order,
-                                (void*)h->d_spill, h->spill_bytes, s, ws, &h->last_kernel);
+                                (void*)h->d_spill, h->spill_bytes, s, ws, &h->last_kernel, d_pparams);
     if (e != hipSuccess) return hip_fail(e, "wide solve launch");
     h->last_ordered = order != nullptr;
     return record_on(h, s);
+}
+
+int mpcg_solve_device_ex(mpcg_handle* h, int64_t B, const double* d_state, const double* d_coeffs, double* d_u0,
+                         double* d_traj, int32_t* d_status, double* d_obj, int32_t* d_iters, int32_t* d_diag,
+                         void* stream) {
+    return solve_device(h, B, d_state, d_coeffs, nullptr, d_u0, d_traj, d_status, d_obj, d_iters, d_diag, stream);
+}
+
+int mpcg_solve_device_pp(mpcg_handle* h, int64_t B, const double* d_state, const double* d_coeffs,
+                         const double* d_pparams, double* d_u0, double* d_traj, int32_t* d_status, double* d_obj,
+                         int32_t* d_iters, int32_t* d_diag, void* stream) {
+    if (B > 0 && !d_pparams) return fail(-1, "pparams is required");
+    return solve_device(h, B, d_state, d_coeffs, d_pparams, d_u0, d_traj, d_status, d_obj, d_iters, d_diag, stream);
 }
 
 int mpcg_solve(mpcg_handle* h, int64_t B, const double* state, const double* coeffs, double* u0, double* traj,
@@ -466,18 +489,24 @@ int mpcg_solve(mpcg_handle* h, int64_t B, const double* state, const double* coe
     return mpcg_solve_ex(h, B, state, coeffs, u0, traj, status, obj, iters, nullptr);
 }
 
-int mpcg_solve_ex(mpcg_handle* h, int64_t B, const double* state, const double* coeffs, double* u0, double* traj,
-                  int32_t* status, double* obj, int32_t* iters, int32_t* diag) {
+// the host solve; pparams: a parameter row per problem (mpcg_solve_pp) or null
+static int solve_host(mpcg_handle* h, int64_t B, const double* state, const double* coeffs, const double* pparams,
+                      double* u0, double* traj, int32_t* status, double* obj, int32_t* iters, int32_t* diag) {
     if (!h) return fail(-1, "null handle");
     if (B < 0) return fail(-1, "negative batch");
     if (B == 0) return 0;
     if (!state || !coeffs || !u0) return fail(-1, "state, coeffs and u0 are required");
     int rc = mpcg_params_check(&h->params);
     if (rc) return rc;
+    if (pparams) {
+        if (h->params.precision != 0) return fail(-1, kNoFp32Rows);
+        rc = mpcg_pparams_check(pparams, B, h->params.model, nullptr);
+        if (rc) return rc;
+    }
     const int N = h->params.steps;
     // io block: state 6 | coeffs 4 | u0 2 | traj 3N | obj 1 | status+iters (2 int32 = 1 double) |
-    // diag (4 int32 = 2 doubles)
-    const size_t per = (size_t)(6 + 4 + 2 + 3 * N + 1 + 1 + 2);
+    // diag (4 int32 = 2 doubles) | the parameter rows 16 (mpcg_solve_pp)
+    const size_t per = (size_t)(6 + 4 + 2 + 3 * N + 1 + 1 + 2) + (pparams ? MPCG_PP_FIELDS : 0);
     const size_t need = per * sizeof(double) * (size_t)B;
     hipError_t e = hipSetDevice(h->device);
     if (e != hipSuccess) return hip_fail(e, "hipSetDevice");
@@ -500,10 +529,13 @@ int mpcg_solve_ex(mpcg_handle* h, int64_t B, const double* state, const double* 
     int32_t* dst = (int32_t*)(dob + B);
     int32_t* dit = dst + B;
     int32_t* ddg = dit + B;
+    double* dpp = (double*)(ddg + 4 * B);
     e = hipMemcpyAsync(ds, state, sizeof(double) * 6 * B, hipMemcpyHostToDevice, h->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(dc, coeffs, sizeof(double) * 4 * B, hipMemcpyHostToDevice, h->stream);
+    if (e == hipSuccess && pparams)
+        e = hipMemcpyAsync(dpp, pparams, sizeof(double) * MPCG_PP_FIELDS * B, hipMemcpyHostToDevice, h->stream);
     if (e != hipSuccess) return hip_fail(e, "hipMemcpy H2D");
-    rc = mpcg_solve_device_ex(h, B, ds, dc, du, dt, dst, dob, dit, diag ? ddg : nullptr, h->stream);
+    rc = solve_device(h, B, ds, dc, pparams ? dpp : nullptr, du, dt, dst, dob, dit, diag ? ddg : nullptr, h->stream);
     if (rc) return rc;
     e = hipMemcpyAsync(u0, du, sizeof(double) * 2 * B, hipMemcpyDeviceToHost, h->stream);
     if (e == hipSuccess && traj)
@@ -519,6 +551,44 @@ int mpcg_solve_ex(mpcg_handle* h, int64_t B, const double* state, const double* 
     e = hipStreamSynchronize(h->stream);
     if (e != hipSuccess) return hip_fail(e, "hipStreamSynchronize");
     return 0;
+}
+
+int mpcg_solve_ex(mpcg_handle* h, int64_t B, const double* state, const double* coeffs, double* u0, double* traj,
+                  int32_t* status, double* obj, int32_t* iters, int32_t* diag) {
+    return solve_host(h, B, state, coeffs, nullptr, u0, traj, status, obj, iters, diag);
+}
+
+int mpcg_solve_pp(mpcg_handle* h, int64_t B, const double* state, const double* coeffs, const double* pparams,
+                  double* u0, double* traj, int32_t* status, double* obj, int32_t* iters, int32_t* diag) {
+    if (B > 0 && !pparams) return fail(-1, "pparams is required");
+    return solve_host(h, B, state, coeffs, pparams, u0, traj, status, obj, iters, diag);
+}
+
+int mpcg_pparams_fill(const mpcg_params* p, int64_t B, double* rows) {
+    if (!p || !rows) return fail(-1, "null argument");
+    if (B < 0) return fail(-1, "negative batch");
+    double row[MPCG_PP_FIELDS];
+    mpcg::pp_row_from(to_ipm(*p), row);
+    for (int64_t b = 0; b < B; ++b) std::memcpy(rows + b * MPCG_PP_FIELDS, row, sizeof row);
+    return 0;
+}
+
+int mpcg_pparams_check(const double* rows, int64_t B, int32_t model, int64_t* bad_row) {
+    if (!rows && B > 0) return fail(-1, "null rows");
+    if (B < 0) return fail(-1, "negative batch");
+    if (model != 0 && model != 1) return fail(-1, "model must be 0 (differential drive) or 1 (bicycle)");
+    for (int64_t b = 0; b < B; ++b)
+        if (!mpcg::pp_row_ok(rows + b * MPCG_PP_FIELDS, model)) {
+            if (bad_row) *bad_row = b;
+            return fail(-1, "parameter row " + std::to_string(b) +
+                                ": every value finite, DT, ANGVEL, MAXTHR, BOUND > 0, weights >= 0" +
+                                (model == 1 ? ", LF > 0" : ""));
+        }
+    return 0;
+}
+
+double mpcg_decelerate(double dist, double v, double max_throttle, double max_speed, double min_speed, double ref_v) {
+    return mpcg::decelerate(dist, v, max_throttle, max_speed, min_speed, ref_v);
 }
 
 int mpcg_preprocess_device(mpcg_handle* h, int64_t B, int32_t M, const double* d_pose, const double* d_vel,
@@ -588,6 +658,63 @@ int mpcg_track_device(mpcg_handle* h, int64_t B, int32_t M, const double* d_pose
     e = mpcg::launch_post(B, h->params.dt, h->params.ref_v, d_vel, u0, d_cmd, (hipStream_t)stream);
     if (e != hipSuccess) return hip_fail(e, "post-processing launch");
     return record_on(h, (hipStream_t)stream);
+}
+
+int mpcg_track_device_goal(mpcg_handle* h, int64_t B, int32_t M, const double* d_pose, const double* d_vel,
+                           const double* d_plan, const double* d_goal, double* d_ref_v, double max_speed,
+                           double min_speed, int32_t delay_mode, double* d_cmd, double* d_traj, int32_t* d_status,
+                           void* stream) {
+    if (!h) return fail(-1, "null handle");
+    if (B < 0) return fail(-1, "negative batch");
+    if (B == 0) return 0;
+    // (every argument error before the first launch: deceleration rewrites ref_v)
+    if (M < 4) return fail(-1, "M (waypoints per robot) must be >= 4");
+    if (!d_cmd || !d_goal || !d_ref_v || !d_pose || !d_vel || !d_plan)
+        return fail(-1, "cmd, goal, ref_v, pose, vel and plan are required");
+    int rc = mpcg_params_check(&h->params);
+    if (rc) return rc;
+    if (h->params.precision != 0) return fail(-1, kNoFp32Rows);
+    if (!std::isfinite(max_speed) || !std::isfinite(min_speed)) return fail(-1, "max_speed and min_speed must be finite");
+    hipError_t e = hipSetDevice(h->device);
+    if (e != hipSuccess) return hip_fail(e, "hipSetDevice");
+    const size_t need = sizeof(double) * 12 * (size_t)B, need_rows = sizeof(double) * MPCG_PP_FIELDS * (size_t)B;
+    if (need > h->trk_bytes || need_rows > h->rows_bytes) {
+        hipDeviceSynchronize();  // the old buffers may be in use on any stream
+        if (need > h->trk_bytes) {
+            if (h->d_trk) hipFree(h->d_trk);
+            h->d_trk = nullptr;
+            h->trk_bytes = 0;
+            e = hipMalloc((void**)&h->d_trk, need);
+            if (e != hipSuccess) return hip_fail(e, "hipMalloc(track buffers)");
+            h->trk_bytes = need;
+        }
+        if (need_rows > h->rows_bytes) {
+            if (h->d_rows) hipFree(h->d_rows);
+            h->d_rows = nullptr;
+            h->rows_bytes = 0;
+            e = hipMalloc((void**)&h->d_rows, need_rows);
+            if (e != hipSuccess) return hip_fail(e, "hipMalloc(parameter rows)");
+            h->rows_bytes = need_rows;
+        }
+    }
+    double* st = h->d_trk;
+    double* cf = st + 6 * B;
+    double* u0 = cf + 4 * B;
+    hipStream_t s = (hipStream_t)stream;
+    rc = order_on(h, s);
+    if (rc) return rc;
+    double row[MPCG_PP_FIELDS];
+    mpcg::pp_row_from(to_ipm(h->params), row);
+    e = mpcg::launch_decelerate(B, d_pose, d_vel, d_goal, d_ref_v, mpcg::decel_throttle(h->params.max_throttle),
+                                max_speed, min_speed, row, h->d_rows, s);
+    if (e != hipSuccess) return hip_fail(e, "deceleration launch");
+    rc = mpcg_preprocess_device(h, B, M, d_pose, d_vel, d_plan, delay_mode, st, cf, stream);
+    if (rc) return rc;
+    rc = solve_device(h, B, st, cf, h->d_rows, u0, d_traj, d_status, nullptr, nullptr, nullptr, stream);
+    if (rc) return rc;
+    e = mpcg::launch_post_pp(B, h->params.dt, d_ref_v, d_vel, u0, d_cmd, s);
+    if (e != hipSuccess) return hip_fail(e, "post-processing launch");
+    return record_on(h, s);
 }
 
 const char* mpcg_last_kernel(const mpcg_handle* h) { return h ? h->last_kernel : ""; }

@@ -33,7 +33,10 @@ struct WideStreams {
 hipError_t launch_wide_solve(const IpmParams& P, int64_t B, const double* state, const double* coeffs, double* u0,
                              double* traj, int32_t* status, double* obj, int32_t* iters, int32_t* diag,
                              const int32_t* order, void* spill, size_t spill_bytes, hipStream_t stream,
-                             const WideStreams& ws = WideStreams(), const char** kernel_name = nullptr);
+                             const WideStreams& ws = WideStreams(), const char** kernel_name = nullptr,
+                             const double* pparams = nullptr);
+// (pparams: a parameter row per problem, [B][16] doubles in include/mpcg.h's MPCG_PP_* order,
+// on the device -- the k_solve_wide_pp / k_resume_wide_pp instances; fp64 only)
 // Solve order (expected-longest first): device buffer bytes for B problems, and the
 // launch that writes the workgroup -> problem map into `buf` (returned in *order).
 size_t wide_sched_bytes(int64_t B);
@@ -47,6 +50,14 @@ hipError_t launch_find_best_path(int64_t B, int M, double dt, int delay_mode, co
                                  const double* plan, double* state, double* coeffs, double* ws, hipStream_t stream);
 hipError_t launch_post(int64_t B, double dt, double ref_v, const double* vel, const double* u0, double* cmd,
                        hipStream_t stream);
+// The tick with a goal per robot (mpcg_track_device_goal): Tracking::deceleration on ref_v [B]
+// (in/out) and each robot's parameter row -- `row`'s 16 doubles with REF_V = ref_v[b] -- into
+// rows [B][16]; the post-processing with the robot's own REF_V.
+hipError_t launch_decelerate(int64_t B, const double* pose, const double* vel, const double* goal, double* ref_v,
+                             double max_throttle, double max_speed, double min_speed, const double* row, double* rows,
+                             hipStream_t stream);
+hipError_t launch_post_pp(int64_t B, double dt, const double* ref_v, const double* vel, const double* u0, double* cmd,
+                          hipStream_t stream);
 
 // The benchmark's synthetic robots (mpcg_synth.hip): the lemniscate's arc-length table (host,
 // once) and the per-robot pose / velocities / plan from (seed, global index)

@@ -1,0 +1,83 @@
+// mpc_ros_amd/csrc/mpcg_pp.h -- per-problem parameter rows (include/mpcg.h MPCG_PP_*): a row's
+// domain check and its fields as IpmParams, and Tracking::deceleration's rule.  Host and device:
+// mpcg_api.cpp (mpcg_pparams_check, mpcg_decelerate) and the kernels (k_solve_wide_pp,
+// k_resume_wide_pp, k_decelerate) run the same code.
+#ifndef MPCG_PP_H
+#define MPCG_PP_H
+
+#include "ipm_core.h"
+#include "mpcg.h"
+
+namespace mpcg {
+
+// CppAD::ipopt::solve_result::internal_error: the ending of a problem whose row is invalid
+constexpr int32_t IPM_INTERNAL_ERROR = 13;
+
+// the domains of mpcg_params_check on one row (the reserved field is not read).  No
+// short-circuit: on the device the row is in registers, and the fifteen tests are one chain of
+// scalar compares, not fifteen branches.
+MPCG_HD bool pp_row_ok(const double* r, int model) {
+    bool ok = true;
+#pragma unroll
+    for (int j = 0; j < MPCG_PP_RESERVED; ++j) ok = ok & (fabs(r[j]) < INFINITY);  // (finite: not NaN either)
+    ok = ok & (r[MPCG_PP_DT] > 0) & (r[MPCG_PP_ANGVEL] > 0) & (r[MPCG_PP_MAXTHR] > 0) & (r[MPCG_PP_BOUND] > 0);
+#pragma unroll
+    for (int j = MPCG_PP_W_CTE; j <= MPCG_PP_W_DA; ++j) ok = ok & (r[j] >= 0);
+    return ok & (model != 1 || r[MPCG_PP_LF] > 0);
+}
+
+// the per-problem fields of P from a row; N, the model and the options stay P's
+MPCG_HD void pp_row_apply(const double* r, IpmParams& P) {
+    P.dt = r[MPCG_PP_DT];
+    P.ref_cte = r[MPCG_PP_REF_CTE];
+    P.ref_eth = r[MPCG_PP_REF_ETHETA];
+    P.ref_v = r[MPCG_PP_REF_V];
+    P.w_cte = r[MPCG_PP_W_CTE];
+    P.w_eth = r[MPCG_PP_W_EPSI];
+    P.w_v = r[MPCG_PP_W_V];
+    P.w_w = r[MPCG_PP_W_ANGVEL];
+    P.w_a = r[MPCG_PP_W_A];
+    P.w_dw = r[MPCG_PP_W_DANGVEL];
+    P.w_da = r[MPCG_PP_W_DA];
+    P.max_w = r[MPCG_PP_ANGVEL];
+    P.max_a = r[MPCG_PP_MAXTHR];
+    P.bound = r[MPCG_PP_BOUND];
+    P.lf = r[MPCG_PP_LF];
+}
+// and back: the row of P
+MPCG_HD void pp_row_from(const IpmParams& P, double* r) {
+    r[MPCG_PP_DT] = P.dt;
+    r[MPCG_PP_REF_CTE] = P.ref_cte;
+    r[MPCG_PP_REF_ETHETA] = P.ref_eth;
+    r[MPCG_PP_REF_V] = P.ref_v;
+    r[MPCG_PP_W_CTE] = P.w_cte;
+    r[MPCG_PP_W_EPSI] = P.w_eth;
+    r[MPCG_PP_W_V] = P.w_v;
+    r[MPCG_PP_W_ANGVEL] = P.w_w;
+    r[MPCG_PP_W_A] = P.w_a;
+    r[MPCG_PP_W_DANGVEL] = P.w_dw;
+    r[MPCG_PP_W_DA] = P.w_da;
+    r[MPCG_PP_ANGVEL] = P.max_w;
+    r[MPCG_PP_MAXTHR] = P.max_a;
+    r[MPCG_PP_BOUND] = P.bound;
+    r[MPCG_PP_LF] = P.lf;
+    r[MPCG_PP_RESERVED] = 0.0;
+}
+
+// Tracking::deceleration (driving_state.cpp:121-141), the quirk kept: the first branch sets
+// max_speed, not speed
+MPCG_HD double decelerate(double dist, double v, double max_throttle, double max_speed, double min_speed,
+                          double ref_v) {
+    if (dist <= v * v / max_throttle) {
+        const double speed = max_throttle * dist;
+        if (speed > ref_v) return max_speed;
+        if (speed < min_speed) return min_speed;
+        return speed;
+    }
+    return ref_v;
+}
+// (the reference clamps its copy of max_throttle, driving_state.cpp:63)
+MPCG_HD double decel_throttle(double max_throttle) { return max_throttle < 0.1 ? 0.1 : max_throttle; }
+
+}  // namespace mpcg
+#endif

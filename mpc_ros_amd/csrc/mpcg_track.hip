@@ -7,7 +7,9 @@
 //   first int(0.3 M) waypoint increments (:214-235), delay-mode state prediction
 //   (:242-256);
 // and the post-processing of the solve (:262-269): w = w0, throttle = a0,
-// speed = min(v_fb + throttle dt, REF_V).
+// speed = min(v_fb + throttle dt, REF_V).  For the tick with a goal per robot
+// (mpcg_track_device_goal) also Tracking::deceleration (:121-141, k_decelerate: each robot's
+// REF_V and parameter row) and the post-processing with the robot's own REF_V (k_post_pp).
 //
 // The QR runs on MAXM-row arrays (the M waypoint rows followed by zero rows, which
 // change no norm or inner product), unrolled so they stay in registers for M <= 16;
@@ -19,6 +21,7 @@
 #include <math.h>
 
 #include "mpcg_internal.h"
+#include "mpcg_pp.h"
 
 namespace mpcg {
 
@@ -229,6 +232,80 @@ __global__ void __launch_bounds__(64) k_post(int64_t B, double dt, double ref_v,
     cmd[p * 3 + 0] = speed;
     cmd[p * 3 + 1] = w;
     cmd[p * 3 + 2] = thr;
+}
+
+// hypot(x, y) correctly rounded (but for values within ~2^-100 of a rounding boundary): x^2 + y^2
+// as an unevaluated sum of two doubles, its square root, and one Newton correction from the
+// exact residual.  A host's libm hypot differs between builds by an ulp (with and without FMA);
+// the deceleration rule hands this distance on as REF_V, so it is pinned to the exact value.
+// Outside the range where the squares neither overflow nor lose bits: the library's hypot.
+__device__ __forceinline__ double hypot_cr(double x, double y) {
+#pragma clang fp contract(off)
+    double a = fabs(x), b = fabs(y);
+    if (a < b) {
+        const double t = a;
+        a = b;
+        b = t;
+    }
+    if (!(a < 1e150) || (b != 0.0 && b < 1e-130)) return hypot(x, y);
+    if (a == 0.0) return 0.0;
+    const double ah = a * a, al = __builtin_fma(a, a, -ah);
+    const double bh = b * b, bl = __builtin_fma(b, b, -bh);
+    const double sh = ah + bh, e = bh - (sh - ah);  // (ah >= bh: the sum's rounding error, exactly)
+    const double sl = e + (al + bl);
+    const double h = sqrt(sh);
+    const double r = __builtin_fma(-h, h, sh) + sl;  // (sh - h^2 is exact for a correctly rounded root)
+    return h + r / (2.0 * h);
+}
+
+// Tracking::deceleration (driving_state.cpp:121-141) for B robots, one per lane: ref_v[b] (in/out,
+// the robot's REF_V map entry) from its distance to its goal and its feedback speed, then the
+// robot's parameter row: the handle's row with REF_V = ref_v[b].
+struct PRow {
+    double f[MPCG_PP_FIELDS];
+};
+__global__ void __launch_bounds__(64) k_decelerate(int64_t B, const double* pose, const double* vel, const double* goal,
+                                                  double* ref_v, double max_throttle, double max_speed,
+                                                  double min_speed, PRow row, double* rows) {
+    const int64_t p = (int64_t)blockIdx.x * 64 + threadIdx.x;
+    if (p >= B) return;
+    const double dist = hypot_cr(pose[p * 3 + 0] - goal[p * 2 + 0], pose[p * 3 + 1] - goal[p * 2 + 1]);
+    const double rv = decelerate(dist, vel[p * 3 + 0], max_throttle, max_speed, min_speed, ref_v[p]);
+    ref_v[p] = rv;
+    double* r = rows + p * MPCG_PP_FIELDS;
+#pragma unroll
+    for (int j = 0; j < MPCG_PP_FIELDS; ++j) r[j] = j == MPCG_PP_REF_V ? rv : row.f[j];
+}
+
+// driving_state.cpp:262-269 with the robot's own REF_V (:267-268 reads the map's current entry)
+__global__ void __launch_bounds__(64) k_post_pp(int64_t B, double dt, const double* ref_v, const double* vel,
+                                               const double* u0, double* cmd) {
+    const int64_t p = (int64_t)blockIdx.x * 64 + threadIdx.x;
+    if (p >= B) return;
+    const double w = u0[p * 2 + 0], thr = u0[p * 2 + 1];
+    double speed = vel[p * 3 + 0] + thr * dt;
+    if (speed >= ref_v[p]) speed = ref_v[p];
+    cmd[p * 3 + 0] = speed;
+    cmd[p * 3 + 1] = w;
+    cmd[p * 3 + 2] = thr;
+}
+
+hipError_t launch_decelerate(int64_t B, const double* pose, const double* vel, const double* goal, double* ref_v,
+                             double max_throttle, double max_speed, double min_speed, const double* row, double* rows,
+                             hipStream_t stream) {
+    if (B <= 0) return hipSuccess;
+    PRow r;
+    for (int j = 0; j < MPCG_PP_FIELDS; ++j) r.f[j] = row[j];
+    hipLaunchKernelGGL(k_decelerate, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, stream, B, pose, vel, goal, ref_v,
+                       max_throttle, max_speed, min_speed, r, rows);
+    return hipGetLastError();
+}
+
+hipError_t launch_post_pp(int64_t B, double dt, const double* ref_v, const double* vel, const double* u0, double* cmd,
+                          hipStream_t stream) {
+    if (B <= 0) return hipSuccess;
+    hipLaunchKernelGGL(k_post_pp, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, stream, B, dt, ref_v, vel, u0, cmd);
+    return hipGetLastError();
 }
 
 hipError_t launch_find_best_path(int64_t B, int M, double dt, int delay_mode, const double* pose, const double* vel,

@@ -69,15 +69,19 @@ constexpr bool kHeadlineOnly = true;
 #else
 constexpr bool kHeadlineOnly = false;
 #endif
-enum InstKind { SOLVE, WARM, RESUME };
+enum InstKind { SOLVE, WARM, RESUME, PP_SOLVE, PP_RESUME };
 template <int KIND, int M, bool S, class T, int NB, bool D, int W>
 static const void* inst_fn() {
-    if constexpr (kHeadlineOnly && !(KIND != WARM && M == 0 && S && sizeof(T) == 8 && NB == 1 && D))
+    if constexpr (kHeadlineOnly && !((KIND == SOLVE || KIND == RESUME) && M == 0 && S && sizeof(T) == 8 && NB == 1 && D))
         return nullptr;
     else if constexpr (KIND == SOLVE)
         return solve_kernel_fn<M, S, T, NB, D, W>();
     else if constexpr (KIND == WARM)
         return warm_kernel_fn<M, S, T, NB, D, W>();
+    else if constexpr (KIND == PP_SOLVE)
+        return pp_solve_kernel_fn<M, S, T, NB, D, W>();
+    else if constexpr (KIND == PP_RESUME)
+        return pp_resume_kernel_fn<M, S, T, NB>();
     else
         return resume_kernel_fn<M, S, T, NB>();
 }
@@ -88,6 +92,12 @@ static const void* inst_fn() {
 static const WideInst kSolveInst[] = {MPCG_WIDE_SOLVE_INSTANCES(MPCG_ENT_SOLVE)};
 static const WideInst kWarmInst[] = {MPCG_WIDE_WARM_INSTANCES(MPCG_ENT_WARM)};
 static const WideInst kResumeInst[] = {MPCG_WIDE_RESUME_INSTANCES(MPCG_ENT_RESUME)};
+// (the per-problem instances: kPPSolveKeys / kPPResumeKeys)
+#define MPCG_ENT_PP_SOLVE(g, M, S, T, NB, D, W) \
+    {inst_fn<PP_SOLVE, M, S, T, NB, D, W>(), MPCG_PP_SOLVE_NAME(M, S, T, NB, D, W)},
+#define MPCG_ENT_PP_RESUME(g, M, S, T, NB) {inst_fn<PP_RESUME, M, S, T, NB, true, 0>(), MPCG_PP_RESUME_NAME(M, S, T, NB)},
+static const WideInst kPPSolveInst[] = {MPCG_WIDE_PP_SOLVE_INSTANCES(MPCG_ENT_PP_SOLVE)};
+static const WideInst kPPResumeInst[] = {MPCG_WIDE_PP_RESUME_INSTANCES(MPCG_ENT_PP_RESUME)};
 // the instance of a key; fn null: the key is none (refused parameters) or not in the library
 template <size_t n>
 static WideInst find_inst(const WideKey (&keys)[n], const WideInst (&inst)[n], const WideKey& k) {
@@ -96,6 +106,9 @@ static WideInst find_inst(const WideKey (&keys)[n], const WideInst (&inst)[n], c
     return WideInst{nullptr, ""};
 }
 WideInst wide_kernel(const IpmParams& P, int64_t B) { return find_inst(kSolveKeys, kSolveInst, solve_key(P, B)); }
+WideInst wide_pp_kernel(const IpmParams& P, int64_t B) {
+    return find_inst(kPPSolveKeys, kPPSolveInst, pp_solve_key(P, B));
+}
 
 // XCDs of the current device (HW_REG_XCC_ID partitions of the workspace slots); 8 on an
 // MI355X in SPX mode, fewer on a partitioned device
@@ -195,6 +208,9 @@ struct PhaseLaunch {
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;
     int64_t nworkers = 0;
     const hipStream_t* origin = nullptr;
+    // per-problem parameter rows [n_prob][16] (inst: a k_solve_wide_pp instance; the resume
+    // launches then take the k_resume_wide_pp instance and the same rows), or null
+    const double* pparams = nullptr;
 };
 // the solver addresses its dynamic LDS from address 0 (wave_dev.h): no static LDS
 static hipError_t set_dynamic_lds(const void* fn, size_t lds) {
@@ -221,7 +237,9 @@ static hipError_t launch_phase(const WideProblem& pb, const PhaseLaunch& L, bool
     const void* fn = L.inst.fn;
     if (!fn) return hipErrorInvalidValue;
     const bool fp32_phase = P.precision == 1 && L.handoff;  // (parks nothing: its endings go to the hand-over)
-    const void* rf = fp32_phase ? nullptr : find_inst(kResumeKeys, kResumeInst, resume_key(P)).fn;
+    const void* rf = fp32_phase  ? nullptr
+                     : L.pparams ? find_inst(kPPResumeKeys, kPPResumeInst, pp_resume_key(P)).fn
+                                 : find_inst(kResumeKeys, kResumeInst, resume_key(P)).fn;
     if (!fp32_phase && !rf) return hipErrorInvalidValue;
     // (every host-side call before the first launch: the device does not wait for the host
     // between the reset kernel and the solver -- ~15 us of a B = 1 solve otherwise)
@@ -241,7 +259,9 @@ static hipError_t launch_phase(const WideProblem& pb, const PhaseLaunch& L, bool
                .ovf_taken = cnt + PhaseLayout::OVF_TAKEN, .ovf_idx = (int64_t*)(L.base + W.ovf.off),
                .nxcc = (int32_t)W.nxcc, .phase = 0, .ent0 = 0, .ovf_mark = 2, .handoff = L.handoff,
                .handoff_stride = L.handoff ? L.handoff_stride : 0};
-    void* args[] = {(void*)&a};
+    // (the per-problem kernels take the rows as a second argument, after WideArgs)
+    const double* rows = L.pparams;
+    void* args[] = {(void*)&a, (void*)&rows};
     // the resume workers: parked problems (the restoration phase) continued by k_resume_wide
     // fork: the resume workers on the aux stream alongside the batch kernel (the fork point is
     // before the batch kernel); join: the stream continues after both (no host
@@ -296,7 +316,7 @@ static hipError_t launch_phase(const WideProblem& pb, const PhaseLaunch& L, bool
     if (W.has_ovf()) {
         WideArgs ao = a;
         ao.phase = 1;
-        void* oargs[] = {(void*)&ao};
+        void* oargs[] = {(void*)&ao, (void*)&rows};
         e = hipLaunchKernel(rf, dim3((unsigned)pc), dim3(64), oargs, lds, L.stream);
         if (e != hipSuccess) return e;
     }
@@ -306,15 +326,19 @@ static hipError_t launch_phase(const WideProblem& pb, const PhaseLaunch& L, bool
 hipError_t launch_wide_solve(const IpmParams& P, int64_t B, const double* state, const double* coeffs, double* u0,
                              double* traj, int32_t* status, double* obj, int32_t* iters, int32_t* diag,
                              const int32_t* order, void* spill, size_t spill_bytes, hipStream_t stream,
-                             const WideStreams& ws, const char** kernel_name) {
+                             const WideStreams& ws, const char** kernel_name, const double* pparams) {
     if (B <= 0) return hipSuccess;
     if (!spill) return hipErrorInvalidValue;
     const SolveLayout W = solve_layout(P, B);
     if (W.total > spill_bytes) return hipErrorInvalidValue;
     const WideProblem pb{state, coeffs, u0, traj, status, obj, iters, diag, B};
-    PhaseLaunch L{.P = P, .inst = wide_kernel(P, B), .B = B, .order = order, .lay = &W.first, .base = (char*)spill,
-                  .stream = stream, .aux = ws.aux, .ev_fork = ws.ev_fork, .ev_join = ws.ev_join};
+    // (per-problem rows: the same workspace -- the per-problem instance has its plain twin's LDS
+    // size and register allocation, so the slot budget is the plain instance's)
+    PhaseLaunch L{.P = P, .inst = pparams ? wide_pp_kernel(P, B) : wide_kernel(P, B), .B = B, .order = order,
+                  .lay = &W.first, .base = (char*)spill, .stream = stream, .aux = ws.aux, .ev_fork = ws.ev_fork,
+                  .ev_join = ws.ev_join, .pparams = pparams};
     if (!L.inst.fn) return hipErrorInvalidValue;
+    if (pparams && W.two) return hipErrorInvalidValue;  // (the fp32 configuration: refused, wide_plan.h pp_solve_key)
     if (kernel_name) *kernel_name = L.inst.name;
     if (!W.two) return launch_phase(pb, L);
     // the fp32 configuration: [the head on aux, in fp64 from the start] the fp32 phase (hand-over,

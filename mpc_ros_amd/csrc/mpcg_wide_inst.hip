@@ -1,7 +1,8 @@
 // mpc_ros_amd/csrc/mpcg_wide_inst.hip -- the solver kernel instances, one group per
-// translation unit: build.py compiles this file once per MPCG_INST value (0..11, in
+// translation unit: build.py compiles this file once per MPCG_INST value (0..19, in
 // parallel) and links the objects into libmpcg.so.  The groups are listed with their
-// instances in wide_plan.h (MPCG_WIDE_SOLVE_INSTANCES / _RESUME_ / _WARM_INSTANCES).
+// instances in wide_plan.h (MPCG_WIDE_SOLVE_INSTANCES / _RESUME_ / _WARM_INSTANCES; groups 12..19:
+// the per-problem instances, MPCG_WIDE_PP_SOLVE_INSTANCES / _PP_RESUME_INSTANCES).
 #include "mpcg_wide_kern.h"
 
 #ifndef MPCG_INST
@@ -25,10 +26,22 @@ namespace mpcg {
     const void* resume_kernel_fn<M, S, T, NB>() {                                            \
         return (const void*)k_resume_wide<M, S, T, NB>;                                       \
     }
+#define MPCG_DEF_PP_SOLVE(g, M, S, T, NB, D, W)                                               \
+    template <>                                                                               \
+    const void* pp_solve_kernel_fn<M, S, T, NB, D, W>() {                                    \
+        return (const void*)k_solve_wide_pp<M, S, T, NB, D, W>;                               \
+    }
+#define MPCG_DEF_PP_RESUME(g, M, S, T, NB)                                                    \
+    template <>                                                                               \
+    const void* pp_resume_kernel_fn<M, S, T, NB>() {                                         \
+        return (const void*)k_resume_wide_pp<M, S, T, NB>;                                    \
+    }
 // (MPCG_SEL_<g>: the instance's definition if g is this unit's group, nothing otherwise)
 #define MPCG_SEL_SOLVE(g, M, S, T, NB, D, W) MPCG_SEL_##g(MPCG_DEF_SOLVE(g, M, S, T, NB, D, W))
 #define MPCG_SEL_RESUME(g, M, S, T, NB) MPCG_SEL_##g(MPCG_DEF_RESUME(g, M, S, T, NB))
 #define MPCG_SEL_WARM(g, M, S, T, NB, D, W) MPCG_SEL_##g(MPCG_DEF_WARM(g, M, S, T, NB, D, W))
+#define MPCG_SEL_PP_SOLVE(g, M, S, T, NB, D, W) MPCG_SEL_##g(MPCG_DEF_PP_SOLVE(g, M, S, T, NB, D, W))
+#define MPCG_SEL_PP_RESUME(g, M, S, T, NB) MPCG_SEL_##g(MPCG_DEF_PP_RESUME(g, M, S, T, NB))
 #if MPCG_INST == 0
 #define MPCG_SEL_0(x) x
 #else
@@ -89,8 +102,50 @@ namespace mpcg {
 #else
 #define MPCG_SEL_11(x)
 #endif
+#if MPCG_INST == 12
+#define MPCG_SEL_12(x) x
+#else
+#define MPCG_SEL_12(x)
+#endif
+#if MPCG_INST == 13
+#define MPCG_SEL_13(x) x
+#else
+#define MPCG_SEL_13(x)
+#endif
+#if MPCG_INST == 14
+#define MPCG_SEL_14(x) x
+#else
+#define MPCG_SEL_14(x)
+#endif
+#if MPCG_INST == 15
+#define MPCG_SEL_15(x) x
+#else
+#define MPCG_SEL_15(x)
+#endif
+#if MPCG_INST == 16
+#define MPCG_SEL_16(x) x
+#else
+#define MPCG_SEL_16(x)
+#endif
+#if MPCG_INST == 17
+#define MPCG_SEL_17(x) x
+#else
+#define MPCG_SEL_17(x)
+#endif
+#if MPCG_INST == 18
+#define MPCG_SEL_18(x) x
+#else
+#define MPCG_SEL_18(x)
+#endif
+#if MPCG_INST == 19
+#define MPCG_SEL_19(x) x
+#else
+#define MPCG_SEL_19(x)
+#endif
 MPCG_WIDE_SOLVE_INSTANCES(MPCG_SEL_SOLVE)
 MPCG_WIDE_RESUME_INSTANCES(MPCG_SEL_RESUME)
 MPCG_WIDE_WARM_INSTANCES(MPCG_SEL_WARM)
+MPCG_WIDE_PP_SOLVE_INSTANCES(MPCG_SEL_PP_SOLVE)
+MPCG_WIDE_PP_RESUME_INSTANCES(MPCG_SEL_PP_RESUME)
 
 }  // namespace mpcg

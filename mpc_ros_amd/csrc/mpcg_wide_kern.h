@@ -13,6 +13,7 @@
 #include <hip/hip_runtime.h>
 
 #include "mpcg_internal.h"
+#include "mpcg_pp.h"
 #include "wave_dev.h"
 #include "wide_core.h"
 #include "wide_plan.h"
@@ -149,6 +150,49 @@ __device__ __forceinline__ void release_slot(int32_t* flags, int s) {
 // as constants.
 template <class Solver>
 __device__ __forceinline__ void write_out(const WideArgs& a, Solver& S, int64_t p, int parked);
+// Row p of the per-problem parameters into registers, once: read through a constant-address-space
+// pointer at a wave-uniform address, so the loads are scalar (s_load_dwordx*) wherever they stand
+// in the kernel -- a plain global pointer gives vector loads once an atomic has preceded them.  The
+// rows are constant for the kernel: the caller keeps them unchanged until the solve has passed.
+// VHOLD (the batch kernel): the values are then moved to VGPRs, lane-replicated, and held there
+// through the solve; otherwise (the resume kernel) they stay wave-uniform and the allocator holds
+// them in SGPRs and SGPR spill slots.  Held in VGPRs the batch kernel measured 0.8-2.7 % faster
+// in every horizon class timed, also where it then spills 5-18 VGPRs (DESIGN.md "Per-problem
+// parameters").
+struct PPRow {
+    double f[MPCG_PP_FIELDS];
+};
+template <bool VHOLD = false>
+__device__ __forceinline__ PPRow pp_load_row(const double* pparams, int64_t p) {
+    typedef const double __attribute__((address_space(4))) cdouble;
+    const cdouble* row = (const cdouble*)(pparams + p * MPCG_PP_FIELDS);
+    PPRow r;
+#pragma unroll
+    for (int j = 0; j < MPCG_PP_FIELDS; ++j) {
+        r.f[j] = row[j];
+        if constexpr (VHOLD) asm("" : "+v"(r.f[j]));
+    }
+    return r;
+}
+// (diagnostic builds: -DMPCG_PP_ROW_SGPR=1 keeps the row wave-uniform in the batch kernel too)
+#ifndef MPCG_PP_ROW_SGPR
+#define MPCG_PP_ROW_SGPR 0
+#endif
+// the ending of a problem whose parameter row is outside mpcg_pparams_check's domains: status 13
+// (internal_error), no iteration, zero controls and trajectory, no objective
+__device__ __forceinline__ void pp_invalid_out(const WideArgs& a, int64_t p) {
+    const int t = threadIdx.x;
+    if (t == 0) {
+        a.u0[p * 2 + 0] = 0.0;
+        a.u0[p * 2 + 1] = 0.0;
+        if (a.status) a.status[p] = IPM_INTERNAL_ERROR;
+        if (a.iters) a.iters[p] = 0;
+        if (a.obj) a.obj[p] = __builtin_nan("");
+    }
+    if (a.diag && t < 4) a.diag[p * 4 + t] = 0;
+    if (a.traj)
+        for (int k = t; k < 3 * a.P.N; k += 64) a.traj[p * 3 * a.P.N + k] = 0.0;
+}
 
 // WPE: wavefronts per SIMD the register allocation is for -- 2 (256 VGPRs), 1 (512) for the
 // instances whose LDS per problem allows at most 4 problems per CU anyway (wide_plan.h), or
@@ -158,8 +202,12 @@ __device__ __forceinline__ void write_out(const WideArgs& a, Solver& S, int64_t 
 // The batch kernels' body: one problem per wavefront.  WARM (the fp64 phase of the fp32
 // configuration, k_warm_wide): the problem continues from the fp32 solver's hand-over
 // (WideSolver::solve_warm) where the fp32 solve converged, else it is solved from the start.
-template <int MODEL, bool SPLIT, class T, int NB, bool DEFOPT, bool WARM>
-__device__ __forceinline__ void solve_body(const WideArgs& a) {
+// PP (k_solve_wide_pp): the per-problem fields of the parameters come from row p of pparams
+// (include/mpcg.h MPCG_PP_*), N, the model and the options from a.P; the row is loaded once by
+// scalar loads (pp_load_row), moved to VGPRs, checked before the solve (pp_invalid_out: no
+// trap) and applied from the same registers.
+template <int MODEL, bool SPLIT, class T, int NB, bool DEFOPT, bool WARM, bool PP = false>
+__device__ __forceinline__ void solve_body(const WideArgs& a, const double* pparams = nullptr) {
     if ((int64_t)blockIdx.x >= a.B) return;
     const int64_t p = a.order ? (int64_t)a.order[blockIdx.x] : (int64_t)blockIdx.x;
     check_index_quiet(p, a.n_prob);
@@ -174,6 +222,15 @@ __device__ __forceinline__ void solve_body(const WideArgs& a) {
     IpmParams Pk = a.P;
     if constexpr (DEFOPT) ipopt_default_options(Pk);
     if (blockIdx.x == 0 && t == 0) atomicExch(a.started, 1);
+    if constexpr (PP) {
+        const PPRow row = pp_load_row<!MPCG_PP_ROW_SGPR>(pparams, p);
+        if (!pp_row_ok(row.f, MODEL)) {
+            pp_invalid_out(a, p);
+            block_done(a.done);
+            return;
+        }
+        pp_row_apply(row.f, Pk);
+    }
     const int slot = claim_slot(a.slot_flags, a.nslots, a.nxcc, (int64_t)blockIdx.x);
     check_index_quiet(slot, a.nslots);
     typedef WideSolver<DevWave, MODEL, SPLIT, T, NB> Solver;
@@ -242,6 +299,13 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE, WP
 template <int MODEL, bool SPLIT, class T, int NB, bool DEFOPT = false, int WPE = 2>
 __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE, WPE))) k_warm_wide(WideArgs a) {
     solve_body<MODEL, SPLIT, T, NB, DEFOPT, true>(a);
+}
+
+// the batch kernel with a parameter row per problem (mpcg_solve_device_pp): pparams [n_prob][16]
+template <int MODEL, bool SPLIT, class T, int NB, bool DEFOPT = false, int WPE = 2>
+__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE, WPE)))
+k_solve_wide_pp(WideArgs a, const double* pparams) {
+    solve_body<MODEL, SPLIT, T, NB, DEFOPT, false, true>(a, pparams);
 }
 
 // results of problem p (u0, status, iterations, objective, trajectory; honor_original_bounds)
@@ -387,6 +451,7 @@ __device__ __forceinline__ int64_t take_overflow(const WideArgs& a) {
 
 // (one wavefront per SIMD: the restoration phase and the resumed solve get the whole
 // register file -- the workers are few, and the drain runs after the batch kernel)
+// (k_resume_wide_pp below is this kernel's twin for per-problem parameters: keep the two in step)
 template <int MODEL, bool SPLIT, class T, int NB>
 __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 1))) k_resume_wide(WideArgs a) {
     const int t = threadIdx.x;
@@ -432,6 +497,56 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 1)))
         write_out(a, S, p, a.phase == 0 ? 1 : a.ovf_mark);
     }
 }
+// k_resume_wide with a parameter row per problem (mpcg_solve_device_pp; fp64, no hand-over): the
+// same parameters as k_solve_wide_pp gave problem p, from row p again (valid: the batch kernel
+// parks or lists only problems it solved).  A copy of k_resume_wide's body but for the
+// parameters and the hand-over -- a change to either kernel's protocol belongs in both.  (A
+// body shared through a function does not keep k_resume_wide's instances' code as it is.)
+template <int MODEL, bool SPLIT, class T, int NB>
+__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 1)))
+k_resume_wide_pp(WideArgs a, const double* pparams) {
+    const int t = threadIdx.x;
+    const WideLayout Lw(a.P.N, a.P.filter_cap, MODEL);
+    typedef WideSolver<DevWave, MODEL, SPLIT, T, NB> Solver;
+    for (;;) {
+        int64_t p;
+        T* ent;
+        if (a.phase == 0) {
+            const int e = take_parked(a);
+            if (e < 0) return;
+            check_index("parked entry", e, a.park_cap);
+            p = a.park_idx[e];
+            check_index("parked problem", p, a.n_prob);
+            ent = (T*)a.park + (int64_t)e * a.park_stride;
+        } else {
+            p = take_overflow(a);
+            if (p < 0) return;
+            check_index("overflow problem", p, a.n_prob);
+            check_index("overflow worker's park entry", (int64_t)a.ent0 + blockIdx.x, a.park_cap);
+            ent = (T*)a.park + (int64_t)(a.ent0 + blockIdx.x) * a.park_stride;
+        }
+        IpmProblem<T> pr;
+#pragma unroll
+        for (int j = 0; j < 6; ++j) pr.init[j] = (T)a.state[p * 6 + j];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) pr.c[j] = (T)a.coeffs[p * 4 + j];
+        DevWave wv;
+        wv.t = t;
+        IpmParams Pk = a.P;
+        const PPRow row = pp_load_row(pparams, p);
+        pp_row_apply(row.f, Pk);
+        Solver S(Pk, pr, wv, ent + Solver::PARK_SCALARS + Lw.total());
+        if (a.phase == 0) {
+            if (!S.park_entry_ok(ent, p)) index_fault("parked entry's tag / counts: problem", p, a.n_prob);
+            S.unpark(ent);
+        } else {
+            S.init();
+            S.run();
+        }
+        S.finish_resto();
+        write_out(a, S, p, a.phase == 0 ? 1 : a.ovf_mark);
+    }
+}
 
 // Kernel instances (host stubs), defined in mpcg_wide_inst.hip: the instance of
 // k_solve_wide<MODEL, SPLIT, T, NB, DEFOPT, WPE> / k_resume_wide<MODEL, SPLIT, T, NB>.
@@ -448,6 +563,12 @@ template <int MODEL, bool SPLIT, class T, int NB>
 const void* resume_kernel_fn();
 template <int MODEL, bool SPLIT, class T, int NB, bool DEFOPT, int WPE>
 const void* warm_kernel_fn();
+// (the per-problem instances, k_solve_wide_pp / k_resume_wide_pp: wide_plan.h pp_solve_key / pp_resume_key)
+template <int MODEL, bool SPLIT, class T, int NB, bool DEFOPT, int WPE>
+const void* pp_solve_kernel_fn();
+template <int MODEL, bool SPLIT, class T, int NB>
+const void* pp_resume_kernel_fn();
+WideInst wide_pp_kernel(const IpmParams& P, int64_t B);
 
 // (the instances the library carries: the lists of wide_plan.h)
 #define MPCG_DECL_SOLVE(g, M, S, T, NB, D, W) template <> const void* solve_kernel_fn<M, S, T, NB, D, W>();
@@ -456,6 +577,12 @@ const void* warm_kernel_fn();
 MPCG_WIDE_SOLVE_INSTANCES(MPCG_DECL_SOLVE)
 MPCG_WIDE_RESUME_INSTANCES(MPCG_DECL_RESUME)
 MPCG_WIDE_WARM_INSTANCES(MPCG_DECL_WARM)
+#define MPCG_DECL_PP_SOLVE(g, M, S, T, NB, D, W) template <> const void* pp_solve_kernel_fn<M, S, T, NB, D, W>();
+#define MPCG_DECL_PP_RESUME(g, M, S, T, NB) template <> const void* pp_resume_kernel_fn<M, S, T, NB>();
+MPCG_WIDE_PP_SOLVE_INSTANCES(MPCG_DECL_PP_SOLVE)
+MPCG_WIDE_PP_RESUME_INSTANCES(MPCG_DECL_PP_RESUME)
+#undef MPCG_DECL_PP_SOLVE
+#undef MPCG_DECL_PP_RESUME
 #undef MPCG_DECL_SOLVE
 #undef MPCG_DECL_WARM
 #undef MPCG_DECL_RESUME

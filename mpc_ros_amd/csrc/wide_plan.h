@@ -49,10 +49,33 @@
     X(10, 0, false, double, 1, true, 2)       \
     X(11, 0, false, double, 1, true, 1)       \
     X(11, 0, false, double, 2, true, 1)
+// Per-problem parameter rows (include/mpcg.h MPCG_PP_*; mpcg_solve_device_pp): the batch kernel
+// k_solve_wide_pp, general options, fp64, one per (model, horizon class) -- and the
+// default-options instance of the benchmark class -- and its resume kernels k_resume_wide_pp:
+// lists and groups of their own (the lists above are what solve_key / resume_key choose from)
+#define MPCG_WIDE_PP_SOLVE_INSTANCES(X)       \
+    X(12, 0, true, double, 1, false, 2)       \
+    X(19, 0, true, double, 1, true, 2)        \
+    X(13, 0, false, double, 1, false, 2)      \
+    X(14, 0, false, double, 1, false, 1)      \
+    X(14, 0, false, double, 2, false, 1)      \
+    X(15, 1, true, double, 1, false, 2)       \
+    X(16, 1, false, double, 1, false, 2)      \
+    X(17, 1, false, double, 1, false, 1)      \
+    X(18, 1, false, double, 2, false, 1)
+#define MPCG_WIDE_PP_RESUME_INSTANCES(X)      \
+    X(12, 0, true, double, 1)                 \
+    X(13, 0, false, double, 1)                \
+    X(15, 0, false, double, 2)                \
+    X(16, 1, true, double, 1)                 \
+    X(17, 1, false, double, 1)                \
+    X(18, 1, false, double, 2)
 // (an instance's name: mpcg_last_kernel() reports the one a solve launched)
 #define MPCG_SOLVE_NAME(M, S, T, NB, D, W) "k_solve_wide<" #M "," #S "," #T "," #NB "," #D "," #W ">"
 #define MPCG_WARM_NAME(M, S, T, NB, D, W) "k_warm_wide<" #M "," #S "," #T "," #NB "," #D "," #W ">"
 #define MPCG_RESUME_NAME(M, S, T, NB) "k_resume_wide<" #M "," #S "," #T "," #NB ">"
+#define MPCG_PP_SOLVE_NAME(M, S, T, NB, D, W) "k_solve_wide_pp<" #M "," #S "," #T "," #NB "," #D "," #W ">"
+#define MPCG_PP_RESUME_NAME(M, S, T, NB) "k_resume_wide_pp<" #M "," #S "," #T "," #NB ">"
 
 namespace mpcg {
 
@@ -86,6 +109,8 @@ struct WideKey {
 inline constexpr WideKey kSolveKeys[] = {MPCG_WIDE_SOLVE_INSTANCES(MPCG_KEY7)};
 inline constexpr WideKey kResumeKeys[] = {MPCG_WIDE_RESUME_INSTANCES(MPCG_KEY5)};
 inline constexpr WideKey kWarmKeys[] = {MPCG_WIDE_WARM_INSTANCES(MPCG_KEY7)};
+inline constexpr WideKey kPPSolveKeys[] = {MPCG_WIDE_PP_SOLVE_INSTANCES(MPCG_KEY7)};
+inline constexpr WideKey kPPResumeKeys[] = {MPCG_WIDE_PP_RESUME_INSTANCES(MPCG_KEY5)};
 #undef MPCG_KEY7
 #undef MPCG_KEY5
 template <size_t n>
@@ -148,6 +173,18 @@ inline WideKey resume_key(const IpmParams& P) {
     const WideClass c = wide_class(P);
     return c.ok ? WideKey{c.model, c.split, false, c.nb, false, 0} : WideKey{};
 }
+// Per-problem parameter rows: the general-options fp64 instance of the horizon class (the rows
+// fix neither the class nor the LDS layout: N, the model and filter_cap are P's), or the
+// default-options one where the library carries it (the benchmark class); the fp32
+// configuration is refused -- its fp64 phase and head would need per-problem instances as well
+inline WideKey pp_solve_key(const IpmParams& P, int64_t /*B*/) {
+    const WideClass c = wide_class(P);
+    if (!c.ok || P.precision != 0) return WideKey{};
+    WideKey k{c.model, c.split, false, c.nb, ipopt_options_are_default(P), c.one ? 1 : 2};
+    if (k.defopt && !has_key(kPPSolveKeys, k)) k.defopt = false;
+    return k;
+}
+inline WideKey pp_resume_key(const IpmParams& P) { return P.precision == 0 ? resume_key(P) : WideKey{}; }
 // the fp64 phase's instance (k_warm_wide, default options) for the horizon class of the fp64
 // parameters Pr (fp64_params): the differential drive only
 inline WideKey warm_key(const IpmParams& Pr) {

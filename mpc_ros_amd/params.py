@@ -33,6 +33,47 @@ PLUGIN_DEFAULTS = {
 }
 
 
+# A per-problem parameter row (include/mpcg.h MPCG_PP_*): these keys in this order, then one
+# reserved 0.  STEPS and MODEL are not in it: they are the batch's.
+ROW_KEYS = ("DT", "REF_CTE", "REF_ETHETA", "REF_V", "W_CTE", "W_EPSI", "W_V", "W_ANGVEL", "W_A", "W_DANGVEL", "W_DA",
+            "ANGVEL", "MAXTHR", "BOUND", "LF")
+ROW_FIELDS = 16
+
+
+def rows(base, B: int | None = None, **per_key):
+    """Parameter rows for a batch, a (B, 16) float64 array in the header's order.
+
+    ``base`` is a sequence of B parameter dicts (one per robot), or one dict for the whole
+    batch with per-key arrays of length B as keywords, e.g. ``rows(P, REF_V=ref_v)`` (B from the
+    arrays, or given).  Keys missing from a dict take PLUGIN_DEFAULTS' value (LF: 0.5, the
+    library's default wheelbase); STEPS, MODEL and unknown keys are ignored, as LoadParams
+    ignores them."""
+    import numpy as np
+
+    def one(d):
+        return [float(d.get(k, PLUGIN_DEFAULTS.get(k, 0.5))) for k in ROW_KEYS] + [0.0]
+
+    if isinstance(base, dict):
+        for k in per_key:
+            if k not in ROW_KEYS:
+                raise KeyError(f"{k!r} is not a per-problem parameter (STEPS and MODEL are the batch's)")
+        lens = {np.shape(v)[0] for v in per_key.values()}
+        if B is not None:
+            lens.add(int(B))
+        if len(lens) != 1:
+            raise ValueError("rows: give B or per-key arrays of one length")
+        out = np.tile(np.asarray(one(base), dtype=np.float64), (lens.pop(), 1))
+        for k, v in per_key.items():
+            out[:, ROW_KEYS.index(k)] = np.asarray(v, dtype=np.float64)
+        return out
+    if per_key:
+        raise ValueError("rows: per-key arrays go with one base dict")
+    out = np.asarray([one(d) for d in base], dtype=np.float64).reshape(-1, ROW_FIELDS)
+    if B is not None and out.shape[0] != int(B):
+        raise ValueError("rows: B differs from the number of dicts")
+    return out
+
+
 def merged(base: dict, overrides: dict | None) -> dict:
     """LoadParams semantics: keys present in ``overrides`` replace, others keep the
     previous value (the ``params.find(k) != end() ? at(k) : old`` pattern of

@@ -130,16 +130,28 @@ class BatchSolver:
         return int(_lib.lib().mpcg_handle_workspace_bytes(self._h, int(B)))
 
     # ----------------------------------------------------------------- solve
-    def solve(self, state: np.ndarray, coeffs: np.ndarray, want_traj: bool = True) -> dict:
+    def solve(self, state: np.ndarray, coeffs: np.ndarray, want_traj: bool = True, params_rows=None) -> dict:
+        """params_rows [B, 16] (params.rows): a parameter row per problem instead of the handle's
+        per-problem fields (mpcg_solve_pp); a row outside the parameters' domains raises."""
         B, out, ptrs = _host_batch(state, coeffs, self.N, want_traj, diag=True)
+        if params_rows is not None:
+            rows = np.ascontiguousarray(params_rows, dtype=np.float64)
+            assert rows.shape == (B, _lib.PP_FIELDS), "params_rows [B,16]"
+            _lib.check(_lib.lib().mpcg_solve_pp(self._h, B, ptrs[0], ptrs[1], rows.ctypes.data_as(C.POINTER(C.c_double)),
+                                                *ptrs[2:]), "mpcg_solve_pp")
+            return out
         _lib.check(_lib.lib().mpcg_solve_ex(self._h, B, *ptrs), "mpcg_solve_ex")
         # diag columns: restoration phases, filter entries dropped beyond its capacity, parked,
         # most filter entries held at once
         return out
 
-    def solve_device(self, state, coeffs, u0, traj=None, status=None, obj=None, iters=None, stream=None, diag=None):
+    def solve_device(self, state, coeffs, u0, traj=None, status=None, obj=None, iters=None, stream=None, diag=None,
+                     pparams=None):
         """All arguments are torch tensors on this handle's GPU (float64 / int32, contiguous);
-        diag [B, 4] int32: restoration phases, filter overflows, parked, filter peak."""
+        diag [B, 4] int32: restoration phases, filter overflows, parked, filter peak.
+        pparams [B, 16] float64: a parameter row per problem (mpcg_solve_device_pp), read when the
+        stream runs the solve -- keep it unchanged until then.  A row outside the parameters'
+        domains ends its problem with status 13, iters 0 and zero outputs."""
         import torch
 
         B = state.shape[0]
@@ -154,6 +166,13 @@ class BatchSolver:
         if stream is None:
             stream = torch.cuda.current_stream(state.device)
         ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None  # noqa: E731
+        if pparams is not None:
+            assert (pparams.is_cuda and pparams.dtype == torch.float64 and pparams.is_contiguous()
+                    and tuple(pparams.shape) == (B, _lib.PP_FIELDS))
+            _lib.check(_lib.lib().mpcg_solve_device_pp(
+                self._h, B, ptr(state), ptr(coeffs), ptr(pparams), ptr(u0), ptr(traj), ptr(status), ptr(obj),
+                ptr(iters), ptr(diag), C.c_void_p(stream.cuda_stream)), "mpcg_solve_device_pp")
+            return
         _lib.check(_lib.lib().mpcg_solve_device_ex(
             self._h, B, ptr(state), ptr(coeffs), ptr(u0), ptr(traj), ptr(status), ptr(obj), ptr(iters), ptr(diag),
             C.c_void_p(stream.cuda_stream)), "mpcg_solve_device_ex")
@@ -196,9 +215,15 @@ class BatchSolver:
             self._h, B, M, ptr(pose), ptr(vel), ptr(plan), int(bool(delay_mode)), ptr(state), ptr(coeffs),
             C.c_void_p(stream.cuda_stream)), "mpcg_preprocess_device")
 
-    def track_device(self, pose, vel, plan, cmd, traj=None, status=None, delay_mode: bool = True, stream=None):
+    def track_device(self, pose, vel, plan, cmd, traj=None, status=None, delay_mode: bool = True, stream=None,
+                     goal=None, ref_v=None, max_speed: float = 0.7, min_speed: float = 0.05):
         """One control tick for B robots: preprocessing, solve, post-processing
-        (driving_state.cpp:175-269).  cmd [B,3] = (speed, w, throttle)."""
+        (driving_state.cpp:175-269).  cmd [B,3] = (speed, w, throttle).
+
+        With goal [B,2] and ref_v [B] (in/out): the tick of mpcComputeVelocityCommands
+        (mpcg_track_device_goal) -- Tracking::deceleration rewrites each robot's REF_V in ref_v
+        from its distance to its goal (max_speed, min_speed: driving_state.cpp:26, :29), the
+        solve and the speed clamp use it; pass ref_v back in at the next tick."""
         import torch
 
         B, M = plan.shape[0], plan.shape[1]
@@ -210,6 +235,16 @@ class BatchSolver:
         if stream is None:
             stream = torch.cuda.current_stream(pose.device)
         ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None  # noqa: E731
+        if (goal is None) != (ref_v is None):
+            raise ValueError("goal and ref_v go together")
+        if goal is not None:
+            for t, shape in ((goal, (B, 2)), (ref_v, (B,))):
+                assert t.is_cuda and t.dtype == torch.float64 and t.is_contiguous() and tuple(t.shape) == shape
+            _lib.check(_lib.lib().mpcg_track_device_goal(
+                self._h, B, M, ptr(pose), ptr(vel), ptr(plan), ptr(goal), ptr(ref_v), float(max_speed), float(min_speed),
+                int(bool(delay_mode)), ptr(cmd), ptr(traj), ptr(status), C.c_void_p(stream.cuda_stream)),
+                "mpcg_track_device_goal")
+            return
         _lib.check(_lib.lib().mpcg_track_device(
             self._h, B, M, ptr(pose), ptr(vel), ptr(plan), int(bool(delay_mode)), ptr(cmd), ptr(traj), ptr(status),
             C.c_void_p(stream.cuda_stream)), "mpcg_track_device")
