@@ -53,6 +53,12 @@ class MpcgXfer(C.Structure):
     _fields_ = [("src_offset", C.c_size_t), ("dst_offset", C.c_size_t), ("bytes", C.c_size_t)]
 
 
+class MpcgRolloutLogs(C.Structure):
+    """mpcg_rollout_logs (include/mpcg.h): the device pointers of a rollout's logs, each may be null."""
+    _fields_ = [(n, C.c_void_p) for n in ("pose", "vel", "cmd", "cursor", "start", "count", "status", "iters",
+                                          "ref_v")]
+
+
 GATHER_ARRAYS = 5  # MPCG_GATHER_ARRAYS
 SIGNATURES = {
     "mpcg_abi_version": ([], C.c_int),
@@ -89,6 +95,18 @@ SIGNATURES = {
     "mpcg_track_device_goal": ([C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                 C.c_void_p, C.c_double, C.c_double, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
                                 C.c_void_p], C.c_int),
+    "mpcg_plan_window_mmax": ([C.c_int32, C.c_int32], C.c_int32),
+    "mpcg_plan_window": ([_dp, C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_int32, C.c_int32, _ip, _ip, _ip, _dp],
+                         C.c_int),
+    "mpcg_plan_window_device": ([C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
+                                 C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
+                                C.c_int),
+    "mpcg_preprocess_device_n": ([C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                  C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p], C.c_int),
+    "mpcg_rollout_device": ([C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
+                             C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_double, C.c_int32, C.c_int32,
+                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(MpcgRolloutLogs),
+                             C.c_void_p], C.c_int),
     "mpcg_solve_multi": ([C.c_int, C.POINTER(C.c_int), _PP, C.c_int64, _dp, _dp, _dp, _dp, _ip, _dp, _ip], C.c_int),
     "mpcg_shard_range": ([C.c_int64, C.c_int, C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int64)], C.c_int),
     "mpcg_multi_gather_plan": ([C.c_int64, C.c_int32, C.c_int, C.c_int, C.c_void_p], C.c_int),

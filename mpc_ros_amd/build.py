@@ -17,7 +17,7 @@ SOURCES = [os.path.join(CSRC, f) for f in ("mpcg_wide.hip", "mpcg_wide_inst.hip"
 INST = os.path.join(CSRC, "mpcg_wide_inst.hip")
 N_INST = 20  # MPCG_INST groups of mpcg_wide_inst.hip (the instance lists of wide_plan.h)
 HEADERS = [os.path.join(CSRC, f) for f in ("ipm_core.h", "wide_core.h", "wide_plan.h", "wave_dev.h", "mpcg_internal.h",
-                                           "mpcg_wide_kern.h", "mpcg_pp.h")] + [
+                                           "mpcg_wide_kern.h", "mpcg_pp.h", "mpcg_window.h")] + [
     os.path.join(ROOT, "include", f) for f in ("mpcg.h", "mpc_planner.h")]
 ARCH = os.environ.get("MPCG_OFFLOAD_ARCH", "gfx950")
 

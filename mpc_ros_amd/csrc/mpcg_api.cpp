@@ -13,6 +13,7 @@
 #include "mpcg.h"
 #include "mpcg_internal.h"
 #include "mpcg_pp.h"
+#include "mpcg_window.h"
 
 namespace {
 thread_local std::string g_err;
@@ -53,6 +54,9 @@ struct mpcg_handle {
     // mpcg_track_device_goal: the robots' parameter rows [B][16]
     double* d_rows = nullptr;
     size_t rows_bytes = 0;
+    // mpcg_rollout_device: the windows' plans [B][Mmax][2] | cmd [B][3] | count [B] | start [B]
+    double* d_roll = nullptr;
+    size_t roll_bytes = 0;
     // preprocessing scratch of plans longer than 64 waypoints
     double* d_pp = nullptr;
     size_t pp_bytes = 0;
@@ -303,6 +307,7 @@ void mpcg_destroy(mpcg_handle* h) {
     if (h->d_io) hipFree(h->d_io);
     if (h->d_trk) hipFree(h->d_trk);
     if (h->d_rows) hipFree(h->d_rows);
+    if (h->d_roll) hipFree(h->d_roll);
     if (h->d_pp) hipFree(h->d_pp);
     if (h->d_sched) hipFree(h->d_sched);
     if (h->d_spill) hipFree(h->d_spill);
@@ -714,6 +719,188 @@ int mpcg_track_device_goal(mpcg_handle* h, int64_t B, int32_t M, const double* d
     if (rc) return rc;
     e = mpcg::launch_post_pp(B, h->params.dt, d_ref_v, d_vel, u0, d_cmd, s);
     if (e != hipSuccess) return hip_fail(e, "post-processing launch");
+    return record_on(h, s);
+}
+
+// ---- the closed loop on the device ----
+
+int32_t mpcg_plan_window_mmax(int32_t window_wp, int32_t stride) {
+    if (window_wp < 1 || stride < 1) return fail(-1, "window_wp and stride must be >= 1");
+    const int64_t m = mpcg::plan_window_mmax(window_wp, stride);
+    if (m > INT32_MAX) return fail(-1, "Mmax = ceil(window_wp / stride) + 1 exceeds int32");
+    return (int32_t)m;
+}
+
+int mpcg_plan_window(const double* course, int32_t G, int32_t cursor, double x, double y, int32_t window_wp,
+                     int32_t stride, int32_t* new_cursor, int32_t* start, int32_t* count, double* plan) {
+    if (!course || !plan) return fail(-1, "course and plan are required");
+    if (G < 1) return fail(-1, "G (course waypoints) must be >= 1");
+    if (cursor < 0 || cursor >= G) return fail(-1, "cursor must be in [0, G)");
+    if (window_wp < 1 || stride < 1) return fail(-1, "window_wp and stride must be >= 1");
+    const int64_t m = mpcg::plan_window_mmax(window_wp, stride);
+    if (m > INT32_MAX) return fail(-1, "Mmax = ceil(window_wp / stride) + 1 exceeds int32");
+    const mpcg::PlanWindow w = mpcg::plan_window(course, G, cursor, x, y, window_wp, stride);
+    mpcg::plan_window_copy(course, w, stride, (int)m, plan);
+    if (new_cursor) *new_cursor = w.cursor;
+    if (start) *start = w.start;
+    if (count) *count = w.count;
+    return 0;
+}
+
+// the window arguments the device calls share; *Mmax on success
+static int window_args_check(int32_t C, int32_t Gmax, int32_t window_wp, int32_t stride, int* Mmax) {
+    if (window_wp < 1 || stride < 1) return fail(-1, "window_wp and stride must be >= 1");
+    if (C < 1 || Gmax < 1) return fail(-1, "C (courses) and Gmax (waypoints per course) must be >= 1");
+    const int64_t m = mpcg::plan_window_mmax(window_wp, stride);
+    if (m > mpcg::kWindowMaxM)
+        return fail(-1, "Mmax = ceil(window_wp / stride) + 1 must be <= 64 (sampled waypoints per robot)");
+    *Mmax = (int)m;
+    return 0;
+}
+
+int mpcg_plan_window_device(mpcg_handle* h, int64_t B, const double* d_courses, const int32_t* d_course_len,
+                            const int32_t* d_course_of, int32_t C, int32_t Gmax, const double* d_pose,
+                            int32_t window_wp, int32_t stride, int32_t* d_cursor, double* d_plan, int32_t* d_count,
+                            void* stream) {
+    if (!h) return fail(-1, "null handle");
+    if (B < 0) return fail(-1, "negative batch");
+    int Mmax = 0;
+    int rc = window_args_check(C, Gmax, window_wp, stride, &Mmax);
+    if (rc) return rc;
+    if (B == 0) return 0;
+    if (!d_courses || !d_course_len || !d_course_of || !d_pose || !d_cursor || !d_plan || !d_count)
+        return fail(-1, "null buffer");
+    hipError_t e = hipSetDevice(h->device);
+    if (e != hipSuccess) return hip_fail(e, "hipSetDevice");
+    e = mpcg::launch_plan_window(B, d_courses, d_course_len, d_course_of, C, Gmax, d_pose, window_wp, stride, Mmax,
+                                 d_cursor, d_plan, d_count, nullptr, (hipStream_t)stream);
+    if (e != hipSuccess) return hip_fail(e, "plan window launch");
+    return 0;
+}
+
+int mpcg_preprocess_device_n(mpcg_handle* h, int64_t B, int32_t Mmax, const double* d_pose, const double* d_vel,
+                             const double* d_plan, const int32_t* d_count, int32_t delay_mode, double* d_state,
+                             double* d_coeffs, void* stream) {
+    if (!h) return fail(-1, "null handle");
+    if (B < 0) return fail(-1, "negative batch");
+    if (Mmax < 1 || Mmax > mpcg::kWindowMaxM) return fail(-1, "Mmax (plan rows per robot) must be in [1, 64]");
+    if (B == 0) return 0;
+    if (!d_pose || !d_vel || !d_plan || !d_count || !d_state || !d_coeffs) return fail(-1, "null buffer");
+    hipError_t e = hipSetDevice(h->device);
+    if (e != hipSuccess) return hip_fail(e, "hipSetDevice");
+    e = mpcg::launch_find_best_path_n(B, Mmax, d_count, h->params.dt, delay_mode ? 1 : 0, d_pose, d_vel, d_plan,
+                                      d_state, d_coeffs, (hipStream_t)stream);
+    if (e != hipSuccess) return hip_fail(e, "find_best_path launch");
+    return 0;
+}
+
+// a handle buffer of at least `need` bytes (grown on first use; the old one may be in use on
+// any stream)
+static int ensure_buffer(mpcg_handle* h, double** buf, size_t* bytes, size_t need, const char* what) {
+    if (need <= *bytes) return 0;
+    hipDeviceSynchronize();
+    if (*buf) hipFree(*buf);
+    *buf = nullptr;
+    *bytes = 0;
+    hipError_t e = hipMalloc((void**)buf, need);
+    if (e != hipSuccess) return hip_fail(e, what);
+    *bytes = need;
+    return 0;
+}
+
+int mpcg_rollout_device(mpcg_handle* h, int64_t B, int32_t K, const double* d_courses, const int32_t* d_course_len,
+                        const int32_t* d_course_of, int32_t C, int32_t Gmax, int32_t window_wp, int32_t stride,
+                        double goal_tol, double max_speed, double min_speed, int32_t delay_mode, int32_t integrate,
+                        double* d_pose, double* d_vel, int32_t* d_cursor, double* d_ref_v, int32_t* d_done,
+                        const mpcg_rollout_logs* logs, void* stream) {
+    if (!h) return fail(-1, "null handle");
+    if (B < 0) return fail(-1, "negative batch");
+    // (every argument error before the first launch: a tick rewrites the robots' state)
+    if (K < 1) return fail(-1, "K (ticks) must be >= 1");
+    int Mmax = 0;
+    int rc = window_args_check(C, Gmax, window_wp, stride, &Mmax);
+    if (rc) return rc;
+    rc = mpcg_params_check(&h->params);
+    if (rc) return rc;
+    if (h->params.precision != 0) return fail(-1, kNoFp32Rows);
+    if (!std::isfinite(max_speed) || !std::isfinite(min_speed)) return fail(-1, "max_speed and min_speed must be finite");
+    if (std::isnan(goal_tol)) return fail(-1, "goal_tol must be a number");
+    if (B == 0) return 0;
+    if (!d_courses || !d_course_len || !d_course_of || !d_pose || !d_vel || !d_cursor || !d_ref_v || !d_done)
+        return fail(-1, "courses, course_len, course_of, pose, vel, cursor, ref_v and done are required");
+    hipError_t e = hipSetDevice(h->device);
+    if (e != hipSuccess) return hip_fail(e, "hipSetDevice");
+    const size_t uB = (size_t)B;
+    rc = ensure_buffer(h, &h->d_trk, &h->trk_bytes, sizeof(double) * 12 * uB, "hipMalloc(track buffers)");
+    if (rc) return rc;
+    rc = ensure_buffer(h, &h->d_rows, &h->rows_bytes, sizeof(double) * MPCG_PP_FIELDS * uB, "hipMalloc(parameter rows)");
+    if (rc) return rc;
+    rc = ensure_buffer(h, &h->d_roll, &h->roll_bytes,
+                       sizeof(double) * (2 * (size_t)Mmax + 3) * uB + sizeof(int32_t) * 2 * uB,
+                       "hipMalloc(rollout buffers)");
+    if (rc) return rc;
+    double* st = h->d_trk;
+    double* cf = st + 6 * B;
+    double* u0 = cf + 4 * B;
+    double* plan = h->d_roll;
+    double* cmd = plan + 2 * (size_t)Mmax * uB;
+    int32_t* count = (int32_t*)(cmd + 3 * B);
+    int32_t* start = count + B;
+    hipStream_t s = (hipStream_t)stream;
+    rc = order_on(h, s);
+    if (rc) return rc;
+    double row[MPCG_PP_FIELDS];
+    mpcg::pp_row_from(to_ipm(h->params), row);
+    const mpcg_rollout_logs none{};
+    const mpcg_rollout_logs& lg = logs ? *logs : none;
+    for (int32_t k = 0; k < K; ++k) {
+        const size_t o = (size_t)k * uB;  // this tick's row of the logs
+        e = mpcg::launch_plan_window(B, d_courses, d_course_len, d_course_of, C, Gmax, d_pose, window_wp, stride, Mmax,
+                                     d_cursor, plan, count, start, s);
+        if (e != hipSuccess) return hip_fail(e, "plan window launch");
+        mpcg::RolloutArgs a{};
+        a.B = B;
+        a.tick = k;
+        a.courses = d_courses;
+        a.course_len = d_course_len;
+        a.course_of = d_course_of;
+        a.C = C;
+        a.Gmax = Gmax;
+        a.goal_tol = goal_tol;
+        a.max_throttle = mpcg::decel_throttle(h->params.max_throttle);
+        a.max_speed = max_speed;
+        a.min_speed = min_speed;
+        a.dt = h->params.dt;
+        a.integrate = integrate ? 1 : 0;
+        a.pose = d_pose;
+        a.vel = d_vel;
+        a.cursor = d_cursor;
+        a.start = start;
+        a.count = count;
+        a.ref_v = d_ref_v;
+        a.done = d_done;
+        a.rows = h->d_rows;
+        a.cmd = cmd;
+        a.log_pose = lg.pose ? lg.pose + 3 * o : nullptr;
+        a.log_vel = lg.vel ? lg.vel + 3 * o : nullptr;
+        a.log_cmd = lg.cmd ? lg.cmd + 3 * o : nullptr;
+        a.log_ref_v = lg.ref_v ? lg.ref_v + o : nullptr;
+        a.log_cursor = lg.cursor ? lg.cursor + o : nullptr;
+        a.log_start = lg.start ? lg.start + o : nullptr;
+        a.log_count = lg.count ? lg.count + o : nullptr;
+        e = mpcg::launch_rollout_begin(a, row, s);
+        if (e != hipSuccess) return hip_fail(e, "rollout tick launch");
+        e = mpcg::launch_find_best_path_n(B, Mmax, count, h->params.dt, delay_mode ? 1 : 0, d_pose, d_vel, plan, st,
+                                          cf, s);
+        if (e != hipSuccess) return hip_fail(e, "find_best_path launch");
+        rc = solve_device(h, B, st, cf, h->d_rows, u0, nullptr, lg.status ? lg.status + o : nullptr, nullptr,
+                          lg.iters ? lg.iters + o : nullptr, nullptr, stream);
+        if (rc) return rc;
+        e = mpcg::launch_post_pp(B, h->params.dt, d_ref_v, d_vel, u0, cmd, s);
+        if (e != hipSuccess) return hip_fail(e, "post-processing launch");
+        e = mpcg::launch_rollout_end(a, s);
+        if (e != hipSuccess) return hip_fail(e, "rollout tick launch");
+    }
     return record_on(h, s);
 }
 

@@ -59,6 +59,46 @@ hipError_t launch_decelerate(int64_t B, const double* pose, const double* vel, c
 hipError_t launch_post_pp(int64_t B, double dt, const double* ref_v, const double* vel, const double* u0, double* cmd,
                           hipStream_t stream);
 
+// The closed loop on the device (mpcg_track.hip; the window rule is mpcg_window.h).
+// The plan window of B robots on C shared courses [C][Gmax][2]: cursor [B] in/out, plan
+// [B][Mmax][2] (rows past the count are 0), count [B], start [B] (may be null).
+hipError_t launch_plan_window(int64_t B, const double* courses, const int32_t* course_len, const int32_t* course_of,
+                              int C, int Gmax, const double* pose, int window_wp, int stride, int Mmax,
+                              int32_t* cursor, double* plan, int32_t* count, int32_t* start, hipStream_t stream);
+// launch_find_best_path with count[p] waypoints for robot p in plan rows of Mmax (<= 64)
+hipError_t launch_find_best_path_n(int64_t B, int Mmax, const int32_t* count, double dt, int delay_mode,
+                                   const double* pose, const double* vel, const double* plan, double* state,
+                                   double* coeffs, hipStream_t stream);
+// One rollout tick around the solve.  begin, after the window: Tracking::deceleration towards
+// the goal (the course's last waypoint), the done mark, the robot's parameter row (`row` with
+// REF_V = ref_v[b]; a done robot's is invalid) and the tick's inputs into the logs.  end, after
+// the post-processing: a done robot's command is 0; the unicycle over one control period; the
+// command into the log.
+struct RolloutArgs {
+    int64_t B;
+    int tick;  // index within this call
+    const double* courses;
+    const int32_t* course_len;
+    const int32_t* course_of;
+    int C, Gmax;
+    double goal_tol, max_throttle, max_speed, min_speed, dt;
+    int integrate;
+    double* pose;           // [B][3] in/out
+    double* vel;            // [B][3] in/out
+    const int32_t* cursor;  // [B] (after the cut)
+    const int32_t* start;   // [B]
+    const int32_t* count;   // [B]
+    double* ref_v;          // [B] in/out
+    int32_t* done;          // [B] in/out
+    double* rows;           // [B][16]
+    const double* cmd;      // [B][3] (the post-processing's)
+    // this tick's rows of the logs, each may be null
+    double *log_pose, *log_vel, *log_cmd, *log_ref_v;
+    int32_t *log_cursor, *log_start, *log_count;
+};
+hipError_t launch_rollout_begin(const RolloutArgs& a, const double* row, hipStream_t stream);
+hipError_t launch_rollout_end(const RolloutArgs& a, hipStream_t stream);
+
 // The benchmark's synthetic robots (mpcg_synth.hip): the lemniscate's arc-length table (host,
 // once) and the per-robot pose / velocities / plan from (seed, global index)
 void synth_arc_table(std::vector<double>& t, std::vector<double>& s);

@@ -10,6 +10,9 @@
 // speed = min(v_fb + throttle dt, REF_V).  For the tick with a goal per robot
 // (mpcg_track_device_goal) also Tracking::deceleration (:121-141, k_decelerate: each robot's
 // REF_V and parameter row) and the post-processing with the robot's own REF_V (k_post_pp).
+// For the closed loop on the device (mpcg_rollout_device): the plan window from a shared course
+// (k_plan_window, the rule of mpcg_window.h), the preprocessing with a waypoint count per robot
+// (k_find_best_path_n) and the two ends of a rollout tick (k_rollout_begin, k_rollout_end).
 //
 // The QR runs on MAXM-row arrays (the M waypoint rows followed by zero rows, which
 // change no norm or inner product), unrolled so they stay in registers for M <= 16;
@@ -22,6 +25,7 @@
 
 #include "mpcg_internal.h"
 #include "mpcg_pp.h"
+#include "mpcg_window.h"
 
 namespace mpcg {
 
@@ -288,6 +292,221 @@ __global__ void __launch_bounds__(64) k_post_pp(int64_t B, double dt, const doub
     cmd[p * 3 + 0] = speed;
     cmd[p * 3 + 1] = w;
     cmd[p * 3 + 2] = thr;
+}
+
+// ---- The closed loop on the device (mpcg_rollout_device): the plan window from a shared course,
+// the preprocessing with a waypoint count per robot, and the two ends of a rollout tick. ----
+
+// MPCPlannerROS::getCutOffPlan and downSamplePlan (mpcg_window.h) for B robots, one per lane, each
+// on one of C shared courses: cursor [B] (in/out), plan [B][Mmax][2] (rows past the count are 0),
+// count [B], start [B] (may be null).  A robot whose course index, course length or cursor is out
+// of range reads no course: count 0, cursor unchanged.
+struct WindowArgs {
+    int64_t B;
+    const double* courses;      // [C][Gmax][2]
+    const int32_t* course_len;  // [C]
+    const int32_t* course_of;   // [B]
+    int C, Gmax;
+    const double* pose;         // [B][3]
+    int window_wp, stride, Mmax;
+    int32_t* cursor;
+    double* plan;
+    int32_t* count;
+    int32_t* start;
+};
+
+// robot p's course, or null where it has none (its index or the course's length out of range)
+__device__ __forceinline__ const double* course_of_robot(const double* courses, const int32_t* course_len,
+                                                         const int32_t* course_of, int C, int Gmax, int64_t p, int* G) {
+    const int co = course_of[p];
+    if (co < 0 || co >= C) return nullptr;
+    *G = course_len[co];
+    if (*G < 1 || *G > Gmax) return nullptr;
+    return courses + (int64_t)co * Gmax * 2;
+}
+
+__global__ void __launch_bounds__(64) k_plan_window(WindowArgs a) {
+    const int64_t p = (int64_t)blockIdx.x * 64 + threadIdx.x;
+    if (p >= a.B) return;
+    int G = 0;
+    const double* course = course_of_robot(a.courses, a.course_len, a.course_of, a.C, a.Gmax, p, &G);
+    const int c = a.cursor[p];
+    PlanWindow w{c, 0, 0, 0};
+    if (course && c >= 0 && c < G)
+        w = plan_window(course, G, c, a.pose[p * 3 + 0], a.pose[p * 3 + 1], a.window_wp, a.stride);
+    plan_window_copy(course, w, a.stride, a.Mmax, a.plan + p * (int64_t)a.Mmax * 2);
+    a.cursor[p] = w.cursor;
+    a.count[p] = w.count;
+    if (a.start) a.start[p] = w.start;
+}
+
+// k_find_best_path with robot p's own waypoint count: a.M is the plan's row stride Mmax
+// (<= MAXM), count[p] the rows that hold waypoints.  The heading from the first int(0.3 count)
+// increments and everything after it use the robot's count.  A robot with fewer than 4 waypoints
+// (polyfit asserts order 3 <= M - 1, driving_state.cpp:286), or a count beyond the stride, is not
+// fitted: its state and coeffs are 0.
+// The wavefront makes one pass per distinct count among its robots, the count wave-uniform in
+// each (the first waiting lane's; the lanes that hold it run the pass): the pass is
+// k_find_best_path's code on a scalar M, so a robot's result does not depend on its neighbours'
+// counts, and a batch of one count is that kernel's arithmetic.  Most robots of a fleet hold a
+// full window, so a wavefront makes one to three passes.
+// (k_find_best_path's body, statement for statement, for one robot)
+template <int MAXM>
+__device__ __forceinline__ void find_best_path_pass(const TrackArgs& a, int64_t p) {
+    const int M = a.M;
+    const double px = a.pose[p * 3 + 0], py = a.pose[p * 3 + 1], theta = a.pose[p * 3 + 2];
+    const double v = a.vel[p * 3 + 0], w = a.vel[p * 3 + 1], throttle = a.vel[p * 3 + 2];
+    const double* pl = a.plan + p * (int64_t)M * 2;
+    const double ct = cos(theta), st = sin(theta);
+    double xv[MAXM], yv[MAXM];
+#pragma unroll
+    for (int i = 0; i < MAXM; ++i) {
+        double dx = 0, dy = 0;
+        if (i < M) {
+            dx = pl[2 * i] - px;
+            dy = pl[2 * i + 1] - py;
+        }
+        xv[i] = dx * ct + dy * st;
+        yv[i] = dy * ct - dx * st;
+    }
+    double c[4];
+    polyfit3<MAXM>(M, xv, yv, c);
+    finish_state(a, p, theta, v, w, throttle, c);
+}
+
+template <int MAXM>
+__global__ void __launch_bounds__(64) k_find_best_path_n(TrackArgs a, const int32_t* count) {
+    const int64_t p = (int64_t)blockIdx.x * 64 + threadIdx.x;
+    if (p >= a.B) return;
+    const int Mp = count[p];
+    if (Mp < 4 || Mp > a.M) {
+        for (int j = 0; j < 6; ++j) a.state[p * 6 + j] = 0.0;
+        for (int j = 0; j < 4; ++j) a.coeffs[p * 4 + j] = 0.0;
+        return;
+    }
+    // (the loop is wave-uniform: todo holds the lanes that still wait, and its lowest lane always
+    // matches its own count, so every pass retires at least that lane)
+    unsigned long long todo = __ballot(1);
+    while (todo) {
+        const int M = __builtin_amdgcn_readlane(Mp, __ffsll(todo) - 1);
+        // (the lanes that hold M, as a mask: under a test `Mp == M` the compiler would put the
+        // lane's own Mp in M's place, and the pass would run on a per-lane count again)
+        const unsigned long long same = __ballot(Mp == M);
+        todo &= ~same;
+        if ((same >> threadIdx.x) & 1) {
+            // (the pass reads robot p's plan at plan + 2 p M: rows of M, here of a.M)
+            TrackArgs r = a;
+            r.M = M;
+            r.plan = a.plan + p * (int64_t)(a.M - M) * 2;
+            find_best_path_pass<MAXM>(r, p);
+        }
+    }
+}
+
+// One rollout tick around the solve.  k_rollout_begin, after the window: Tracking::deceleration
+// towards the goal (the course's last waypoint), the done mark, the robot's parameter row and the
+// tick's inputs into the logs.  k_rollout_end, after the post-processing: the command of a done
+// robot is 0; the unicycle over one control period; the command into the log.
+// (RolloutArgs: mpcg_internal.h)
+
+__global__ void __launch_bounds__(64) k_rollout_begin(RolloutArgs a, PRow row) {
+    const int64_t p = (int64_t)blockIdx.x * 64 + threadIdx.x;
+    if (p >= a.B) return;
+    int G = 0;
+    const double* course = course_of_robot(a.courses, a.course_len, a.course_of, a.C, a.Gmax, p, &G);
+    const double x = a.pose[p * 3 + 0], y = a.pose[p * 3 + 1], v = a.vel[p * 3 + 0];
+    double rv = a.ref_v[p];
+    bool at_goal = false;
+    if (course) {
+        const double dist = hypot_cr(x - course[2 * (G - 1)], y - course[2 * (G - 1) + 1]);
+        rv = decelerate(dist, v, a.max_throttle, a.max_speed, a.min_speed, rv);
+        a.ref_v[p] = rv;
+        at_goal = dist <= a.goal_tol;
+    }
+    const int n = a.count[p];
+    int dn = a.done[p];
+    if (dn == 0 && (n < 4 || at_goal)) {
+        dn = a.tick + 1;
+        a.done[p] = dn;
+    }
+    // a done robot's row is invalid (DT = 0): the solve's row validation ends its problem at
+    // iteration 0 with status 13 and zero controls
+    double* r = a.rows + p * MPCG_PP_FIELDS;
+#pragma unroll
+    for (int j = 0; j < MPCG_PP_FIELDS; ++j)
+        r[j] = j == MPCG_PP_REF_V ? rv : (j == MPCG_PP_DT && dn != 0) ? 0.0 : row.f[j];
+    if (a.log_pose)
+        for (int j = 0; j < 3; ++j) a.log_pose[p * 3 + j] = a.pose[p * 3 + j];
+    if (a.log_vel)
+        for (int j = 0; j < 3; ++j) a.log_vel[p * 3 + j] = a.vel[p * 3 + j];
+    if (a.log_ref_v) a.log_ref_v[p] = rv;
+    if (a.log_cursor) a.log_cursor[p] = a.cursor[p];
+    if (a.log_start) a.log_start[p] = a.start[p];
+    if (a.log_count) a.log_count[p] = n;
+}
+
+__global__ void __launch_bounds__(64) k_rollout_end(RolloutArgs a) {
+    const int64_t p = (int64_t)blockIdx.x * 64 + threadIdx.x;
+    if (p >= a.B) return;
+    const bool dn = a.done[p] != 0;
+    const double speed = dn ? 0.0 : a.cmd[p * 3 + 0];
+    const double w = dn ? 0.0 : a.cmd[p * 3 + 1];
+    const double thr = dn ? 0.0 : a.cmd[p * 3 + 2];
+    if (a.log_cmd) {
+        a.log_cmd[p * 3 + 0] = speed;
+        a.log_cmd[p * 3 + 1] = w;
+        a.log_cmd[p * 3 + 2] = thr;
+    }
+    if (!a.integrate) return;
+    if (!dn) {  // (a done robot's pose is frozen)
+        const double yaw = a.pose[p * 3 + 2];
+        a.pose[p * 3 + 0] += speed * cos(yaw) * a.dt;
+        a.pose[p * 3 + 1] += speed * sin(yaw) * a.dt;
+        const double next = yaw + w * a.dt;
+        a.pose[p * 3 + 2] = atan2(sin(next), cos(next));
+    }
+    a.vel[p * 3 + 0] = speed;
+    a.vel[p * 3 + 1] = w;
+    a.vel[p * 3 + 2] = thr;
+}
+
+static dim3 lane_grid(int64_t B) { return dim3((unsigned)((B + 63) / 64)); }
+
+hipError_t launch_plan_window(int64_t B, const double* courses, const int32_t* course_len, const int32_t* course_of,
+                              int C, int Gmax, const double* pose, int window_wp, int stride, int Mmax,
+                              int32_t* cursor, double* plan, int32_t* count, int32_t* start, hipStream_t stream) {
+    if (B <= 0) return hipSuccess;
+    const WindowArgs a{B, courses, course_len, course_of, C, Gmax, pose, window_wp, stride, Mmax, cursor, plan, count,
+                       start};
+    hipLaunchKernelGGL(k_plan_window, lane_grid(B), dim3(64), 0, stream, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_find_best_path_n(int64_t B, int Mmax, const int32_t* count, double dt, int delay_mode,
+                                   const double* pose, const double* vel, const double* plan, double* state,
+                                   double* coeffs, hipStream_t stream) {
+    if (B <= 0) return hipSuccess;
+    if (Mmax > kWindowMaxM) return hipErrorInvalidValue;
+    const TrackArgs a{B, Mmax, dt, delay_mode, pose, vel, plan, state, coeffs};
+    if (Mmax <= 16)
+        hipLaunchKernelGGL(k_find_best_path_n<16>, lane_grid(B), dim3(64), 0, stream, a, count);
+    else
+        hipLaunchKernelGGL(k_find_best_path_n<64>, lane_grid(B), dim3(64), 0, stream, a, count);
+    return hipGetLastError();
+}
+
+hipError_t launch_rollout_begin(const RolloutArgs& a, const double* row, hipStream_t stream) {
+    if (a.B <= 0) return hipSuccess;
+    PRow r;
+    for (int j = 0; j < MPCG_PP_FIELDS; ++j) r.f[j] = row[j];
+    hipLaunchKernelGGL(k_rollout_begin, lane_grid(a.B), dim3(64), 0, stream, a, r);
+    return hipGetLastError();
+}
+
+hipError_t launch_rollout_end(const RolloutArgs& a, hipStream_t stream) {
+    if (a.B <= 0) return hipSuccess;
+    hipLaunchKernelGGL(k_rollout_end, lane_grid(a.B), dim3(64), 0, stream, a);
+    return hipGetLastError();
 }
 
 hipError_t launch_decelerate(int64_t B, const double* pose, const double* vel, const double* goal, double* ref_v,

@@ -198,11 +198,13 @@ class BatchSolver:
         return pose, vel, plan
 
     # ------------------------------------------------ the caller side on the device
-    def preprocess_device(self, pose, vel, plan, state, coeffs, delay_mode: bool = True, stream=None):
+    def preprocess_device(self, pose, vel, plan, state, coeffs, delay_mode: bool = True, stream=None, count=None):
         """Tracking::findBestPath's preprocessing (driving_state.cpp:175-256) for B robots.
 
         pose [B,3] (x, y, yaw), vel [B,3] (v feedback, previous w, previous throttle),
-        plan [B,M,2] -> state [B,6], coeffs [B,4]; torch float64 tensors on this GPU."""
+        plan [B,M,2] -> state [B,6], coeffs [B,4]; torch float64 tensors on this GPU.
+        count [B] int32: robot p's own waypoint count in its M <= 64 plan rows
+        (mpcg_preprocess_device_n); a robot with count < 4 is not fitted, its outputs are 0."""
         import torch
 
         B, M = plan.shape[0], plan.shape[1]
@@ -211,6 +213,12 @@ class BatchSolver:
         if stream is None:
             stream = torch.cuda.current_stream(pose.device)
         ptr = lambda t: C.c_void_p(t.data_ptr())  # noqa: E731
+        if count is not None:
+            assert count.is_cuda and count.dtype == torch.int32 and count.is_contiguous() and tuple(count.shape) == (B,)
+            _lib.check(_lib.lib().mpcg_preprocess_device_n(
+                self._h, B, M, ptr(pose), ptr(vel), ptr(plan), ptr(count), int(bool(delay_mode)), ptr(state),
+                ptr(coeffs), C.c_void_p(stream.cuda_stream)), "mpcg_preprocess_device_n")
+            return
         _lib.check(_lib.lib().mpcg_preprocess_device(
             self._h, B, M, ptr(pose), ptr(vel), ptr(plan), int(bool(delay_mode)), ptr(state), ptr(coeffs),
             C.c_void_p(stream.cuda_stream)), "mpcg_preprocess_device")
@@ -248,6 +256,91 @@ class BatchSolver:
         _lib.check(_lib.lib().mpcg_track_device(
             self._h, B, M, ptr(pose), ptr(vel), ptr(plan), int(bool(delay_mode)), ptr(cmd), ptr(traj), ptr(status),
             C.c_void_p(stream.cuda_stream)), "mpcg_track_device")
+
+    # ------------------------------------------------ the closed loop on the device
+    @staticmethod
+    def _courses(courses, course_len, course_of, B):
+        import torch
+
+        Cn, Gmax = courses.shape[0], courses.shape[1]
+        assert courses.is_cuda and courses.dtype == torch.float64 and courses.is_contiguous()
+        assert tuple(courses.shape) == (Cn, Gmax, 2)
+        for t, n in ((course_len, Cn), (course_of, B)):
+            assert t.is_cuda and t.dtype == torch.int32 and t.is_contiguous() and tuple(t.shape) == (n,)
+        return Cn, Gmax
+
+    def plan_window_device(self, courses, course_len, course_of, pose, window_wp: int, stride: int, cursor, plan,
+                           count, stream=None):
+        """The plan window of B robots (mpcg_plan_window_device; the rule: closed_loop.plan_window):
+        courses [C,Gmax,2] float64, course_len [C] and course_of [B] int32, pose [B,3]; cursor [B]
+        int32 in/out, plan [B,Mmax,2] float64 and count [B] int32 out, Mmax =
+        closed_loop.plan_window_mmax(window_wp, stride)."""
+        import torch
+
+        B = pose.shape[0]
+        Cn, Gmax = self._courses(courses, course_len, course_of, B)
+        Mmax = plan.shape[1]
+        for t, shape, dt in ((pose, (B, 3), torch.float64), (plan, (B, Mmax, 2), torch.float64),
+                             (cursor, (B,), torch.int32), (count, (B,), torch.int32)):
+            assert t.is_cuda and t.dtype == dt and t.is_contiguous() and tuple(t.shape) == shape
+        want = _lib.lib().mpcg_plan_window_mmax(int(window_wp), int(stride))
+        assert want < 0 or Mmax == want, f"plan must have Mmax = {want} rows per robot"
+        if stream is None:
+            stream = torch.cuda.current_stream(pose.device)
+        ptr = lambda t: C.c_void_p(t.data_ptr())  # noqa: E731
+        _lib.check(_lib.lib().mpcg_plan_window_device(
+            self._h, B, ptr(courses), ptr(course_len), ptr(course_of), Cn, Gmax, ptr(pose), int(window_wp), int(stride),
+            ptr(cursor), ptr(plan), ptr(count), C.c_void_p(stream.cuda_stream)), "mpcg_plan_window_device")
+
+    ROLLOUT_LOGS = {"pose": 3, "vel": 3, "cmd": 3, "cursor": 0, "start": 0, "count": 0, "status": 0, "iters": 0,
+                    "ref_v": 0}
+
+    def rollout_logs(self, K: int, B: int, names=None) -> dict:
+        """Log tensors for rollout(K, ..., logs=): pose, vel, cmd [K,B,3] and ref_v [K,B] float64,
+        cursor, start, count, status, iters [K,B] int32 (all of them, or the names given)."""
+        import torch
+
+        dev = torch.device("cuda", self.device)
+        out = {}
+        for n in (names if names is not None else self.ROLLOUT_LOGS):
+            w = self.ROLLOUT_LOGS[n]
+            dt = torch.float64 if w or n == "ref_v" else torch.int32
+            out[n] = torch.zeros((K, B, w) if w else (K, B), dtype=dt, device=dev)
+        return out
+
+    def rollout(self, K: int, courses, course_len, course_of, window_wp: int, stride: int, pose, vel, cursor, ref_v,
+                done, goal_tol: float = 0.1, max_speed: float = 0.7, min_speed: float = 0.05,
+                delay_mode: bool = True, integrate: bool = True, logs: dict | None = None, stream=None):
+        """K control ticks of B robots in one enqueue (mpcg_rollout_device): per tick the plan
+        window from the robot's course, deceleration towards the course's last waypoint, the
+        preprocessing with the robot's own waypoint count, the solve, the post-processing and,
+        with `integrate`, the unicycle of closed_loop.run.  pose [B,3], vel [B,3], ref_v [B]
+        float64 and cursor [B], done [B] int32 are in/out: done[b] is the tick (index + 1) at
+        which robot b stopped, at its goal (within goal_tol) or at its course's end.  logs: tensors
+        by name as rollout_logs(K, B) makes them.  No host synchronisation; call it once before
+        capturing it in a graph (the handle's buffers grow on first use)."""
+        import torch
+
+        B = pose.shape[0]
+        Cn, Gmax = self._courses(courses, course_len, course_of, B)
+        for t, shape, dt in ((pose, (B, 3), torch.float64), (vel, (B, 3), torch.float64), (ref_v, (B,), torch.float64),
+                             (cursor, (B,), torch.int32), (done, (B,), torch.int32)):
+            assert t.is_cuda and t.dtype == dt and t.is_contiguous() and tuple(t.shape) == shape
+        lg = _lib.MpcgRolloutLogs()
+        for n, t in (logs or {}).items():
+            w = self.ROLLOUT_LOGS[n]
+            dt = torch.float64 if w or n == "ref_v" else torch.int32
+            assert t.is_cuda and t.dtype == dt and t.is_contiguous()
+            assert tuple(t.shape) == ((K, B, w) if w else (K, B)), n
+            setattr(lg, n, t.data_ptr())
+        if stream is None:
+            stream = torch.cuda.current_stream(pose.device)
+        ptr = lambda t: C.c_void_p(t.data_ptr())  # noqa: E731
+        _lib.check(_lib.lib().mpcg_rollout_device(
+            self._h, B, int(K), ptr(courses), ptr(course_len), ptr(course_of), Cn, Gmax, int(window_wp), int(stride),
+            float(goal_tol), float(max_speed), float(min_speed), int(bool(delay_mode)), int(bool(integrate)),
+            ptr(pose), ptr(vel), ptr(cursor), ptr(ref_v), ptr(done), C.byref(lg), C.c_void_p(stream.cuda_stream)),
+            "mpcg_rollout_device")
 
 
 class MultiSolver:
