@@ -33,6 +33,16 @@ int hip_fail(hipError_t e, const char* what) {
 }
 }  // namespace
 
+// a device buffer of a handle: only ever grown (ensure)
+struct DevBuf {
+    void* p = nullptr;
+    size_t bytes = 0;
+    template <class T>
+    T* at(const mpcg::Region& r) const {
+        return (T*)((char*)p + r.off);
+    }
+};
+
 struct mpcg_handle {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -44,30 +54,16 @@ struct mpcg_handle {
     hipStream_t aux2 = nullptr;
     hipEvent_t ev_join2 = nullptr;
     mpcg_params params{};
-    // staging buffers for mpcg_solve (host pointers)
-    double* d_io = nullptr;
-    size_t io_bytes = 0;
     int strategy = MPCG_STRATEGY_AUTO;
-    // mpcg_track_device intermediates: state [B][6] | coeffs [B][4] | u0 [B][2]
-    double* d_trk = nullptr;
-    size_t trk_bytes = 0;
-    // mpcg_track_device_goal: the robots' parameter rows [B][16]
-    double* d_rows = nullptr;
-    size_t rows_bytes = 0;
-    // mpcg_rollout_device: the windows' plans [B][Mmax][2] | cmd [B][3] | count [B] | start [B]
-    double* d_roll = nullptr;
-    size_t roll_bytes = 0;
-    // preprocessing scratch of plans longer than 64 waypoints
-    double* d_pp = nullptr;
-    size_t pp_bytes = 0;
-    // solve-order buffers (keys, indices, sort scratch)
-    void* d_sched = nullptr;
-    size_t sched_bytes = 0;
-    // HBM workspace slots of the solver's rare paths and restoration phase (one per resident wavefront)
-    double* d_spill = nullptr;
-    size_t spill_bytes = 0;
-    // stream ordering of the scratch above: the last stream that used it and an event
-    // recorded after that use
+    // The handle's device buffers (grown by ensure, freed by mpcg_destroy):
+    //   io     staging of mpcg_solve's host arrays
+    //   tick   a control tick's intermediates (wide_plan.h TickLayout)
+    //   pp     preprocessing scratch of plans longer than 64 waypoints
+    //   sched  solve-order buffers (keys, indices, sort scratch)
+    //   spill  HBM workspace slots of the solver's rare paths and restoration phase
+    DevBuf d_io, d_tick, d_pp, d_sched, d_spill;
+    // stream ordering of the scratch above (with_scratch): the last stream that used it and an
+    // event recorded after that use
     hipStream_t last_stream = nullptr;
     hipEvent_t last_ev = nullptr;
     bool have_last = false;
@@ -304,13 +300,8 @@ void mpcg_destroy(mpcg_handle* h) {
     hipSetDevice(h->device);
     if (h->stream) hipStreamSynchronize(h->stream);
     if (h->have_last) hipEventSynchronize(h->last_ev);
-    if (h->d_io) hipFree(h->d_io);
-    if (h->d_trk) hipFree(h->d_trk);
-    if (h->d_rows) hipFree(h->d_rows);
-    if (h->d_roll) hipFree(h->d_roll);
-    if (h->d_pp) hipFree(h->d_pp);
-    if (h->d_sched) hipFree(h->d_sched);
-    if (h->d_spill) hipFree(h->d_spill);
+    for (DevBuf* b : {&h->d_io, &h->d_tick, &h->d_pp, &h->d_sched, &h->d_spill})
+        if (b->p) hipFree(b->p);
     if (h->d_arc) hipFree(h->d_arc);
     if (h->aux) hipStreamSynchronize(h->aux);
     if (h->aux2) hipStreamSynchronize(h->aux2);
@@ -344,45 +335,42 @@ static mpcg::IpmParams handle_ipm(const mpcg_handle* h) {
     return P;
 }
 
-static int ensure_spill(mpcg_handle* h, int64_t B) {
-    const size_t need = mpcg::wide_spill_bytes(handle_ipm(h), B);
-    if (need <= h->spill_bytes) return 0;
+// Buffer b of at least `need` bytes.  One rule: nothing to do if it is large enough; otherwise
+// the handle's device, a device synchronise only where an old buffer is freed (it may be in use on
+// any stream), and the allocation.
+static int ensure(mpcg_handle* h, DevBuf& b, size_t need, const char* what) {
+    if (need <= b.bytes) return 0;
     hipSetDevice(h->device);
-    if (h->d_spill) {
-        hipDeviceSynchronize();  // may be in use on any stream
-        hipFree(h->d_spill);
-        h->d_spill = nullptr;
-        h->spill_bytes = 0;
+    if (b.p) {
+        hipDeviceSynchronize();
+        hipFree(b.p);
+        b = DevBuf{};
     }
-    hipError_t e = hipMalloc((void**)&h->d_spill, need);
-    if (e != hipSuccess) return hip_fail(e, "hipMalloc(spill areas)");
-    h->spill_bytes = need;
+    hipError_t e = hipMalloc(&b.p, need);
+    if (e != hipSuccess) {
+        b.p = nullptr;
+        return hip_fail(e, what);
+    }
+    b.bytes = need;
     return 0;
 }
 
-static int ensure_sched(mpcg_handle* h, int64_t B) {
-    const size_t need = mpcg::wide_sched_bytes(B);
-    if (need <= h->sched_bytes) return 0;
-    hipSetDevice(h->device);
-    if (h->d_sched) {
-        hipDeviceSynchronize();  // may be in use on any stream
-        hipFree(h->d_sched);
-        h->d_sched = nullptr;
-        h->sched_bytes = 0;
-    }
-    hipError_t e = hipMalloc(&h->d_sched, need);
-    if (e != hipSuccess) return hip_fail(e, "hipMalloc(schedule buffers)");
-    h->sched_bytes = need;
-    return 0;
+// the solver's scratch for a batch of B: the workspace slots and, for an ordered batch, the
+// solve-order buffers
+static int ensure_solve(mpcg_handle* h, int64_t B) {
+    int rc = ensure(h, h->d_spill, mpcg::wide_spill_bytes(handle_ipm(h), B), "hipMalloc(spill areas)");
+    if (rc || B <= kOrderMinBatch) return rc;
+    return ensure(h, h->d_sched, mpcg::wide_sched_bytes(B), "hipMalloc(schedule buffers)");
 }
 
 // 160 KiB of LDS per CU: up to N = 64 a problem leaves room for a second wavefront (and
 // eight fit at N = 20); up to N = 128 (two stage blocks) one problem may take the CU's LDS
 static const size_t kWideLdsMax = 160 * 1024;
 
-// The handle's scratch (solve order, spill areas, track intermediates) is used
-// stream-ordered: work queued on stream s first waits for the scratch's last use on
-// another stream, and an event marks each use.
+// The handle's scratch (solve order, spill areas, tick intermediates) is used stream-ordered:
+// work queued on stream s first waits for the scratch's last use on another stream, and an event
+// marks each use.  with_scratch is the one place that does both: `queue` launches the work, and
+// whatever it returns -- also a failure after its first launch -- the use is recorded.
 static int order_on(mpcg_handle* h, hipStream_t s) {
     if (h->have_last && h->last_stream != s) {
         hipError_t e = hipStreamWaitEvent(s, h->last_ev, 0);
@@ -397,16 +385,30 @@ static int record_on(mpcg_handle* h, hipStream_t s) {
     h->have_last = true;
     return 0;
 }
+extern "C++" template <class Queue>  // (a template has C++ linkage, also in this block)
+static int with_scratch(mpcg_handle* h, hipStream_t s, Queue&& queue) {
+    int rc = order_on(h, s);
+    if (rc) return rc;
+    rc = queue();
+    if (rc == 0) return record_on(h, s);
+    const std::string err = g_err;  // (the failure's message, not the record's)
+    record_on(h, s);
+    return fail(rc, err);
+}
 
 static bool wave_fits(const mpcg::IpmParams& P) { return P.N <= 128 && mpcg::wide_lds_bytes(P) <= kWideLdsMax; }
 
-int mpcg_reserve(mpcg_handle* h, int64_t B) {
+// the prologue of the calls that take a handle and a batch
+static int batch_check(const mpcg_handle* h, int64_t B) {
     if (!h) return fail(-1, "null handle");
     if (B < 0) return fail(-1, "negative batch");
-    if (B == 0) return 0;
-    int rc = ensure_spill(h, B);
-    if (rc) return rc;
-    return B > kOrderMinBatch ? ensure_sched(h, B) : 0;
+    return 0;
+}
+
+int mpcg_reserve(mpcg_handle* h, int64_t B) {
+    int rc = batch_check(h, B);
+    if (rc || B == 0) return rc;
+    return ensure_solve(h, B);
 }
 
 int mpcg_set_strategy(mpcg_handle* h, int32_t strategy) {
@@ -430,38 +432,29 @@ int mpcg_solve_device(mpcg_handle* h, int64_t B, const double* d_state, const do
 static const char kNoFp32Rows[] =
     "precision 1 (fp32) takes no per-problem parameter rows: its fp64 phase and head have no per-problem instances";
 
-// the device solve; d_pparams: a parameter row per problem (mpcg_solve_device_pp) or null
-static int solve_device(mpcg_handle* h, int64_t B, const double* d_state, const double* d_coeffs,
-                        const double* d_pparams, double* d_u0, double* d_traj, int32_t* d_status, double* d_obj,
-                        int32_t* d_iters, int32_t* d_diag, void* stream) {
-    if (!h) return fail(-1, "null handle");
-    if (B < 0) return fail(-1, "negative batch");
-    if (B == 0) return 0;
-    if (!d_state || !d_coeffs || !d_u0) return fail(-1, "state, coeffs and u0 are required");
+// The refusals of a solve with the handle's parameters (rows: with a parameter row per problem),
+// in two parts: the ticks check arguments of their own between them, in the order they always had
+static int params_refusal(const mpcg_handle* h, bool rows) {
     int rc = mpcg_params_check(&h->params);
     if (rc) return rc;
-    if (d_pparams && h->params.precision != 0) return fail(-1, kNoFp32Rows);
-    hipError_t e = hipSetDevice(h->device);
-    if (e != hipSuccess) return hip_fail(e, "hipSetDevice");
-    hipStream_t s = (hipStream_t)stream;  // NULL = the null stream, as in HIP
-    const mpcg::IpmParams P = handle_ipm(h);
-    if (!wave_fits(P)) return fail(-1, "STEPS must be <= 128 (the problem state must fit the CU's 160 KiB of LDS)");
-    rc = ensure_spill(h, B);
-    if (rc) return rc;
-    if (B > kOrderMinBatch) {
-        rc = ensure_sched(h, B);
-        if (rc) return rc;
-    }
-    rc = order_on(h, s);
-    if (rc) return rc;
+    return rows && h->params.precision != 0 ? fail(-1, kNoFp32Rows) : 0;
+}
+static int lds_refusal(const mpcg_handle* h) {
+    if (wave_fits(handle_ipm(h))) return 0;
+    return fail(-1, "STEPS must be <= 128 (the problem state must fit the CU's 160 KiB of LDS)");
+}
+
+// Queues the solve on s; d_pparams: a parameter row per problem or null.  The caller has passed
+// the refusals, grown the solver's scratch (ensure_solve) and ordered s (with_scratch).
+static int queue_solve(mpcg_handle* h, int64_t B, const double* d_state, const double* d_coeffs,
+                       const double* d_pparams, double* d_u0, double* d_traj, int32_t* d_status, double* d_obj,
+                       int32_t* d_iters, int32_t* d_diag, hipStream_t s) {
     // batches larger than the resident wavefronts (8 per CU) are solved in
     // expected-longest-first order (launch_wide_order)
-    const int32_t* order = nullptr;
+    int32_t* order = nullptr;
     if (B > kOrderMinBatch) {
-        int32_t* ord = nullptr;
-        e = mpcg::launch_wide_order(B, d_coeffs, h->d_sched, h->sched_bytes, &ord, s);
+        hipError_t e = mpcg::launch_wide_order(B, d_coeffs, h->d_sched.p, h->d_sched.bytes, &order, s);
         if (e != hipSuccess) return hip_fail(e, "solve-order sort");
-        order = ord;
     }
     mpcg::WideStreams ws;
     ws.aux = h->aux;
@@ -469,11 +462,32 @@ static int solve_device(mpcg_handle* h, int64_t B, const double* d_state, const 
     ws.ev_fork = h->ev_fork;
     ws.ev_join = h->ev_join;
     ws.ev_join2 = h->ev_join2;
-    e = mpcg::launch_wide_solve(P, B, d_state, d_coeffs, d_u0, d_traj, d_status, d_obj, d_iters, d_diag, order,
-                                (void*)h->d_spill, h->spill_bytes, s, ws, &h->last_kernel, d_pparams);
+    hipError_t e = mpcg::launch_wide_solve(handle_ipm(h), B, d_state, d_coeffs, d_u0, d_traj, d_status, d_obj, d_iters,
+                                           d_diag, order, h->d_spill.p, h->d_spill.bytes, s, ws, &h->last_kernel,
+                                           d_pparams);
     if (e != hipSuccess) return hip_fail(e, "wide solve launch");
     h->last_ordered = order != nullptr;
-    return record_on(h, s);
+    return 0;
+}
+
+// the device solve; d_pparams: a parameter row per problem (mpcg_solve_device_pp) or null
+static int solve_device(mpcg_handle* h, int64_t B, const double* d_state, const double* d_coeffs,
+                        const double* d_pparams, double* d_u0, double* d_traj, int32_t* d_status, double* d_obj,
+                        int32_t* d_iters, int32_t* d_diag, void* stream) {
+    int rc = batch_check(h, B);
+    if (rc || B == 0) return rc;
+    if (!d_state || !d_coeffs || !d_u0) return fail(-1, "state, coeffs and u0 are required");
+    rc = params_refusal(h, d_pparams != nullptr);
+    if (rc) return rc;
+    hipError_t e = hipSetDevice(h->device);
+    if (e != hipSuccess) return hip_fail(e, "hipSetDevice");
+    hipStream_t s = (hipStream_t)stream;  // NULL = the null stream, as in HIP
+    rc = lds_refusal(h);
+    if (rc == 0) rc = ensure_solve(h, B);
+    if (rc) return rc;
+    return with_scratch(h, s, [&] {
+        return queue_solve(h, B, d_state, d_coeffs, d_pparams, d_u0, d_traj, d_status, d_obj, d_iters, d_diag, s);
+    });
 }
 
 int mpcg_solve_device_ex(mpcg_handle* h, int64_t B, const double* d_state, const double* d_coeffs, double* d_u0,
@@ -497,11 +511,10 @@ int mpcg_solve(mpcg_handle* h, int64_t B, const double* state, const double* coe
 // the host solve; pparams: a parameter row per problem (mpcg_solve_pp) or null
 static int solve_host(mpcg_handle* h, int64_t B, const double* state, const double* coeffs, const double* pparams,
                       double* u0, double* traj, int32_t* status, double* obj, int32_t* iters, int32_t* diag) {
-    if (!h) return fail(-1, "null handle");
-    if (B < 0) return fail(-1, "negative batch");
-    if (B == 0) return 0;
+    int rc = batch_check(h, B);
+    if (rc || B == 0) return rc;
     if (!state || !coeffs || !u0) return fail(-1, "state, coeffs and u0 are required");
-    int rc = mpcg_params_check(&h->params);
+    rc = mpcg_params_check(&h->params);
     if (rc) return rc;
     if (pparams) {
         if (h->params.precision != 0) return fail(-1, kNoFp32Rows);
@@ -515,18 +528,9 @@ static int solve_host(mpcg_handle* h, int64_t B, const double* state, const doub
     const size_t need = per * sizeof(double) * (size_t)B;
     hipError_t e = hipSetDevice(h->device);
     if (e != hipSuccess) return hip_fail(e, "hipSetDevice");
-    if (need > h->io_bytes) {
-        if (h->d_io) {
-            hipStreamSynchronize(h->stream);
-            hipFree(h->d_io);
-            h->d_io = nullptr;
-            h->io_bytes = 0;
-        }
-        e = hipMalloc((void**)&h->d_io, need);
-        if (e != hipSuccess) return hip_fail(e, "hipMalloc(io)");
-        h->io_bytes = need;
-    }
-    double* ds = h->d_io;
+    rc = ensure(h, h->d_io, need, "hipMalloc(io)");
+    if (rc) return rc;
+    double* ds = (double*)h->d_io.p;
     double* dc = ds + 6 * B;
     double* du = dc + 4 * B;
     double* dt = du + 2 * B;
@@ -596,137 +600,147 @@ double mpcg_decelerate(double dist, double v, double max_throttle, double max_sp
     return mpcg::decelerate(dist, v, max_throttle, max_speed, min_speed, ref_v);
 }
 
+// ---- the control tick: preprocessing, solve, post-processing ----
+
+// findBestPath returns without solving for an empty plan (driving_state.cpp:182-185);
+// polyfit asserts order 3 <= M - 1 (:286); any longer plan is taken (beyond 64
+// waypoints through an HBM workspace)
+static const char kShortPlan[] = "M (waypoints per robot) must be >= 4";
+
+// the preprocessing scratch of a plan of M waypoints for every robot (none up to 64)
+static int ensure_pp(mpcg_handle* h, int64_t B, int M) {
+    return ensure(h, h->d_pp, mpcg::find_best_path_ws_bytes(B, M), "hipMalloc(preprocessing scratch)");
+}
+// Queues findBestPath's preprocessing on s, for mpcg_preprocess_device(_n) and the tick.  d_count
+// null: M waypoints for every robot, any M >= 4 (beyond 64 through the scratch, which the caller
+// has grown: ensure_pp); else d_count[b] waypoints for robot b in plan rows of M <= 64.
+static int queue_preprocess(mpcg_handle* h, int64_t B, int M, const int32_t* d_count, const double* d_pose,
+                            const double* d_vel, const double* d_plan, int delay_mode, double* d_state,
+                            double* d_coeffs, hipStream_t s) {
+    hipError_t e = mpcg::launch_find_best_path(B, M, d_count, h->params.dt, delay_mode ? 1 : 0, d_pose, d_vel, d_plan,
+                                               d_state, d_coeffs, (double*)h->d_pp.p, s);
+    return e == hipSuccess ? 0 : hip_fail(e, "find_best_path launch");
+}
+
 int mpcg_preprocess_device(mpcg_handle* h, int64_t B, int32_t M, const double* d_pose, const double* d_vel,
                            const double* d_plan, int32_t delay_mode, double* d_state, double* d_coeffs,
                            void* stream) {
-    if (!h) return fail(-1, "null handle");
-    if (B < 0) return fail(-1, "negative batch");
-    if (B == 0) return 0;
-    // findBestPath returns without solving for an empty plan (driving_state.cpp:182-185);
-    // polyfit asserts order 3 <= M - 1 (:286); any longer plan is taken (beyond 64
-    // waypoints through an HBM workspace)
-    if (M < 4) return fail(-1, "M (waypoints per robot) must be >= 4");
+    int rc = batch_check(h, B);
+    if (rc || B == 0) return rc;
+    if (M < 4) return fail(-1, kShortPlan);
     if (!d_pose || !d_vel || !d_plan || !d_state || !d_coeffs) return fail(-1, "null buffer");
     hipError_t e = hipSetDevice(h->device);
     if (e != hipSuccess) return hip_fail(e, "hipSetDevice");
     hipStream_t s = (hipStream_t)stream;
-    const size_t need = mpcg::find_best_path_ws_bytes(B, M);
-    if (need > h->pp_bytes) {
-        if (h->d_pp) {
-            hipDeviceSynchronize();  // the old scratch may be in use on any stream
-            hipFree(h->d_pp);
-            h->d_pp = nullptr;
-            h->pp_bytes = 0;
-        }
-        e = hipMalloc((void**)&h->d_pp, need);
-        if (e != hipSuccess) return hip_fail(e, "hipMalloc(preprocessing scratch)");
-        h->pp_bytes = need;
-    }
-    int rc = need ? order_on(h, s) : 0;
+    rc = ensure_pp(h, B, M);
     if (rc) return rc;
-    e = mpcg::launch_find_best_path(B, M, h->params.dt, delay_mode ? 1 : 0, d_pose, d_vel, d_plan, d_state,
-                                    d_coeffs, h->d_pp, s);
-    if (e != hipSuccess) return hip_fail(e, "find_best_path launch");
-    return need ? record_on(h, s) : 0;
+    auto queue = [&] { return queue_preprocess(h, B, M, nullptr, d_pose, d_vel, d_plan, delay_mode, d_state, d_coeffs, s); };
+    // (up to 64 waypoints it touches none of the handle's scratch)
+    return mpcg::find_best_path_ws_bytes(B, M) ? with_scratch(h, s, queue) : queue();
+}
+
+// One tick's inputs and outputs (device pointers)
+static_assert(mpcg::kRowFields == MPCG_PP_FIELDS, "TickLayout's rows are parameter rows");
+struct Tick {
+    int64_t B;
+    int M;                 // plan rows per robot
+    const double* pose;    // [B][3]
+    const double* vel;     // [B][3]
+    const double* plan;    // [B][M][2]
+    const int32_t* count;  // [B] robot b's waypoints in its M rows, or null: M for every robot
+    int delay_mode;
+    const double* rows;    // [B][16] a parameter row per robot, or null: the handle's parameters
+    const double* ref_v;   // [B] the speed clamp of each robot, or null: the handle's REF_V
+    double* cmd;           // [B][3]
+    double* traj;          // [B][3][N], or null
+    int32_t* status;       // [B], or null
+    int32_t* iters;        // [B], or null
+};
+
+// Everything a call of ticks allocates, before its first launch: the tick scratch of layout L,
+// the preprocessing scratch of a uniform plan of M waypoints (0: a count per robot) and the solver's
+static int ensure_tick(mpcg_handle* h, const mpcg::TickLayout& L, int64_t B, int M) {
+    int rc = ensure(h, h->d_tick, L.total, "hipMalloc(track buffers)");
+    if (rc == 0) rc = ensure_pp(h, B, M);
+    return rc ? rc : ensure_solve(h, B);
+}
+
+// Queues one tick on s: the three stages through the scratch regions of L.  The caller has passed
+// the refusals, called ensure_tick and ordered s (with_scratch).  Rows or none, the solver's
+// instance follows: k_solve_wide_pp or k_solve_wide.
+static int tick(mpcg_handle* h, const Tick& t, const mpcg::TickLayout& L, hipStream_t s) {
+    double *st = h->d_tick.at<double>(L.state), *cf = h->d_tick.at<double>(L.coeffs), *u0 = h->d_tick.at<double>(L.u0);
+    int rc = queue_preprocess(h, t.B, t.M, t.count, t.pose, t.vel, t.plan, t.delay_mode, st, cf, s);
+    if (rc == 0) rc = queue_solve(h, t.B, st, cf, t.rows, u0, t.traj, t.status, nullptr, t.iters, nullptr, s);
+    if (rc) return rc;
+    hipError_t e = mpcg::launch_post(t.B, h->params.dt, h->params.ref_v, t.ref_v, t.vel, u0, t.cmd, s);
+    return e == hipSuccess ? 0 : hip_fail(e, "post-processing launch");
 }
 
 int mpcg_track_device(mpcg_handle* h, int64_t B, int32_t M, const double* d_pose, const double* d_vel,
                       const double* d_plan, int32_t delay_mode, double* d_cmd, double* d_traj, int32_t* d_status,
                       void* stream) {
-    if (!h) return fail(-1, "null handle");
-    if (B < 0) return fail(-1, "negative batch");
-    if (B == 0) return 0;
+    int rc = batch_check(h, B);
+    if (rc || B == 0) return rc;
     if (!d_cmd) return fail(-1, "cmd is required");
     hipError_t e = hipSetDevice(h->device);
     if (e != hipSuccess) return hip_fail(e, "hipSetDevice");
-    const size_t need = sizeof(double) * 12 * (size_t)B;
-    if (need > h->trk_bytes) {
-        if (h->d_trk) {
-            hipDeviceSynchronize();  // the old buffers may be in use on any stream
-            hipFree(h->d_trk);
-            h->d_trk = nullptr;
-            h->trk_bytes = 0;
-        }
-        e = hipMalloc((void**)&h->d_trk, need);
-        if (e != hipSuccess) return hip_fail(e, "hipMalloc(track buffers)");
-        h->trk_bytes = need;
-    }
-    double* st = h->d_trk;
-    double* cf = st + 6 * B;
-    double* u0 = cf + 4 * B;
-    int rc = order_on(h, (hipStream_t)stream);
+    if (M < 4) return fail(-1, kShortPlan);
+    if (!d_pose || !d_vel || !d_plan) return fail(-1, "null buffer");
+    rc = params_refusal(h, false);
+    if (rc == 0) rc = lds_refusal(h);
+    const mpcg::TickLayout L(B, 0, 0);
+    if (rc == 0) rc = ensure_tick(h, L, B, M);
     if (rc) return rc;
-    rc = mpcg_preprocess_device(h, B, M, d_pose, d_vel, d_plan, delay_mode, st, cf, stream);
-    if (rc) return rc;
-    rc = mpcg_solve_device(h, B, st, cf, u0, d_traj, d_status, nullptr, nullptr, stream);
-    if (rc) return rc;
-    e = mpcg::launch_post(B, h->params.dt, h->params.ref_v, d_vel, u0, d_cmd, (hipStream_t)stream);
-    if (e != hipSuccess) return hip_fail(e, "post-processing launch");
-    return record_on(h, (hipStream_t)stream);
+    const Tick t{B, M, d_pose, d_vel, d_plan, nullptr, delay_mode, nullptr, nullptr, d_cmd, d_traj, d_status, nullptr};
+    hipStream_t s = (hipStream_t)stream;
+    return with_scratch(h, s, [&] { return tick(h, t, L, s); });
 }
+
+static const char kSpeedsFinite[] = "max_speed and min_speed must be finite";
 
 int mpcg_track_device_goal(mpcg_handle* h, int64_t B, int32_t M, const double* d_pose, const double* d_vel,
                            const double* d_plan, const double* d_goal, double* d_ref_v, double max_speed,
                            double min_speed, int32_t delay_mode, double* d_cmd, double* d_traj, int32_t* d_status,
                            void* stream) {
-    if (!h) return fail(-1, "null handle");
-    if (B < 0) return fail(-1, "negative batch");
-    if (B == 0) return 0;
-    // (every argument error before the first launch: deceleration rewrites ref_v)
-    if (M < 4) return fail(-1, "M (waypoints per robot) must be >= 4");
+    int rc = batch_check(h, B);
+    if (rc || B == 0) return rc;
+    // (every refusal before the first launch: deceleration rewrites ref_v)
+    if (M < 4) return fail(-1, kShortPlan);
     if (!d_cmd || !d_goal || !d_ref_v || !d_pose || !d_vel || !d_plan)
         return fail(-1, "cmd, goal, ref_v, pose, vel and plan are required");
-    int rc = mpcg_params_check(&h->params);
+    rc = params_refusal(h, true);
     if (rc) return rc;
-    if (h->params.precision != 0) return fail(-1, kNoFp32Rows);
-    if (!std::isfinite(max_speed) || !std::isfinite(min_speed)) return fail(-1, "max_speed and min_speed must be finite");
+    if (!std::isfinite(max_speed) || !std::isfinite(min_speed)) return fail(-1, kSpeedsFinite);
     hipError_t e = hipSetDevice(h->device);
     if (e != hipSuccess) return hip_fail(e, "hipSetDevice");
-    const size_t need = sizeof(double) * 12 * (size_t)B, need_rows = sizeof(double) * MPCG_PP_FIELDS * (size_t)B;
-    if (need > h->trk_bytes || need_rows > h->rows_bytes) {
-        hipDeviceSynchronize();  // the old buffers may be in use on any stream
-        if (need > h->trk_bytes) {
-            if (h->d_trk) hipFree(h->d_trk);
-            h->d_trk = nullptr;
-            h->trk_bytes = 0;
-            e = hipMalloc((void**)&h->d_trk, need);
-            if (e != hipSuccess) return hip_fail(e, "hipMalloc(track buffers)");
-            h->trk_bytes = need;
-        }
-        if (need_rows > h->rows_bytes) {
-            if (h->d_rows) hipFree(h->d_rows);
-            h->d_rows = nullptr;
-            h->rows_bytes = 0;
-            e = hipMalloc((void**)&h->d_rows, need_rows);
-            if (e != hipSuccess) return hip_fail(e, "hipMalloc(parameter rows)");
-            h->rows_bytes = need_rows;
-        }
-    }
-    double* st = h->d_trk;
-    double* cf = st + 6 * B;
-    double* u0 = cf + 4 * B;
+    rc = lds_refusal(h);
+    const mpcg::TickLayout L(B, 0, 1);
+    if (rc == 0) rc = ensure_tick(h, L, B, M);
+    if (rc) return rc;
+    double* rows = h->d_tick.at<double>(L.rows);
+    const Tick t{B, M, d_pose, d_vel, d_plan, nullptr, delay_mode, rows, d_ref_v, d_cmd, d_traj, d_status, nullptr};
     hipStream_t s = (hipStream_t)stream;
-    rc = order_on(h, s);
-    if (rc) return rc;
-    double row[MPCG_PP_FIELDS];
-    mpcg::pp_row_from(to_ipm(h->params), row);
-    e = mpcg::launch_decelerate(B, d_pose, d_vel, d_goal, d_ref_v, mpcg::decel_throttle(h->params.max_throttle),
-                                max_speed, min_speed, row, h->d_rows, s);
-    if (e != hipSuccess) return hip_fail(e, "deceleration launch");
-    rc = mpcg_preprocess_device(h, B, M, d_pose, d_vel, d_plan, delay_mode, st, cf, stream);
-    if (rc) return rc;
-    rc = solve_device(h, B, st, cf, h->d_rows, u0, d_traj, d_status, nullptr, nullptr, nullptr, stream);
-    if (rc) return rc;
-    e = mpcg::launch_post_pp(B, h->params.dt, d_ref_v, d_vel, u0, d_cmd, s);
-    if (e != hipSuccess) return hip_fail(e, "post-processing launch");
-    return record_on(h, s);
+    return with_scratch(h, s, [&] {
+        e = mpcg::launch_decelerate(B, d_pose, d_vel, d_goal, d_ref_v, mpcg::decel_throttle(h->params.max_throttle),
+                                    max_speed, min_speed, mpcg::pp_row_pack(to_ipm(h->params)), rows, s);
+        return e == hipSuccess ? tick(h, t, L, s) : hip_fail(e, "deceleration launch");
+    });
 }
 
 // ---- the closed loop on the device ----
 
-int32_t mpcg_plan_window_mmax(int32_t window_wp, int32_t stride) {
+// Mmax = ceil(window_wp / stride) + 1 of a plan window's arguments
+static int window_mmax(int32_t window_wp, int32_t stride, int64_t* Mmax) {
     if (window_wp < 1 || stride < 1) return fail(-1, "window_wp and stride must be >= 1");
-    const int64_t m = mpcg::plan_window_mmax(window_wp, stride);
+    *Mmax = mpcg::plan_window_mmax(window_wp, stride);
+    return 0;
+}
+
+int32_t mpcg_plan_window_mmax(int32_t window_wp, int32_t stride) {
+    int64_t m = 0;
+    const int rc = window_mmax(window_wp, stride, &m);
+    if (rc) return rc;
     if (m > INT32_MAX) return fail(-1, "Mmax = ceil(window_wp / stride) + 1 exceeds int32");
     return (int32_t)m;
 }
@@ -736,11 +750,10 @@ int mpcg_plan_window(const double* course, int32_t G, int32_t cursor, double x, 
     if (!course || !plan) return fail(-1, "course and plan are required");
     if (G < 1) return fail(-1, "G (course waypoints) must be >= 1");
     if (cursor < 0 || cursor >= G) return fail(-1, "cursor must be in [0, G)");
-    if (window_wp < 1 || stride < 1) return fail(-1, "window_wp and stride must be >= 1");
-    const int64_t m = mpcg::plan_window_mmax(window_wp, stride);
-    if (m > INT32_MAX) return fail(-1, "Mmax = ceil(window_wp / stride) + 1 exceeds int32");
+    const int32_t m = mpcg_plan_window_mmax(window_wp, stride);
+    if (m < 0) return m;
     const mpcg::PlanWindow w = mpcg::plan_window(course, G, cursor, x, y, window_wp, stride);
-    mpcg::plan_window_copy(course, w, stride, (int)m, plan);
+    mpcg::plan_window_copy(course, w, stride, m, plan);
     if (new_cursor) *new_cursor = w.cursor;
     if (start) *start = w.start;
     if (count) *count = w.count;
@@ -749,9 +762,10 @@ int mpcg_plan_window(const double* course, int32_t G, int32_t cursor, double x, 
 
 // the window arguments the device calls share; *Mmax on success
 static int window_args_check(int32_t C, int32_t Gmax, int32_t window_wp, int32_t stride, int* Mmax) {
-    if (window_wp < 1 || stride < 1) return fail(-1, "window_wp and stride must be >= 1");
+    int64_t m = 0;
+    const int rc = window_mmax(window_wp, stride, &m);
+    if (rc) return rc;
     if (C < 1 || Gmax < 1) return fail(-1, "C (courses) and Gmax (waypoints per course) must be >= 1");
-    const int64_t m = mpcg::plan_window_mmax(window_wp, stride);
     if (m > mpcg::kWindowMaxM)
         return fail(-1, "Mmax = ceil(window_wp / stride) + 1 must be <= 64 (sampled waypoints per robot)");
     *Mmax = (int)m;
@@ -762,12 +776,11 @@ int mpcg_plan_window_device(mpcg_handle* h, int64_t B, const double* d_courses, 
                             const int32_t* d_course_of, int32_t C, int32_t Gmax, const double* d_pose,
                             int32_t window_wp, int32_t stride, int32_t* d_cursor, double* d_plan, int32_t* d_count,
                             void* stream) {
-    if (!h) return fail(-1, "null handle");
-    if (B < 0) return fail(-1, "negative batch");
-    int Mmax = 0;
-    int rc = window_args_check(C, Gmax, window_wp, stride, &Mmax);
+    int rc = batch_check(h, B);
     if (rc) return rc;
-    if (B == 0) return 0;
+    int Mmax = 0;
+    rc = window_args_check(C, Gmax, window_wp, stride, &Mmax);
+    if (rc || B == 0) return rc;
     if (!d_courses || !d_course_len || !d_course_of || !d_pose || !d_cursor || !d_plan || !d_count)
         return fail(-1, "null buffer");
     hipError_t e = hipSetDevice(h->device);
@@ -781,31 +794,15 @@ int mpcg_plan_window_device(mpcg_handle* h, int64_t B, const double* d_courses, 
 int mpcg_preprocess_device_n(mpcg_handle* h, int64_t B, int32_t Mmax, const double* d_pose, const double* d_vel,
                              const double* d_plan, const int32_t* d_count, int32_t delay_mode, double* d_state,
                              double* d_coeffs, void* stream) {
-    if (!h) return fail(-1, "null handle");
-    if (B < 0) return fail(-1, "negative batch");
+    int rc = batch_check(h, B);
+    if (rc) return rc;
     if (Mmax < 1 || Mmax > mpcg::kWindowMaxM) return fail(-1, "Mmax (plan rows per robot) must be in [1, 64]");
     if (B == 0) return 0;
     if (!d_pose || !d_vel || !d_plan || !d_count || !d_state || !d_coeffs) return fail(-1, "null buffer");
     hipError_t e = hipSetDevice(h->device);
     if (e != hipSuccess) return hip_fail(e, "hipSetDevice");
-    e = mpcg::launch_find_best_path_n(B, Mmax, d_count, h->params.dt, delay_mode ? 1 : 0, d_pose, d_vel, d_plan,
-                                      d_state, d_coeffs, (hipStream_t)stream);
-    if (e != hipSuccess) return hip_fail(e, "find_best_path launch");
-    return 0;
-}
-
-// a handle buffer of at least `need` bytes (grown on first use; the old one may be in use on
-// any stream)
-static int ensure_buffer(mpcg_handle* h, double** buf, size_t* bytes, size_t need, const char* what) {
-    if (need <= *bytes) return 0;
-    hipDeviceSynchronize();
-    if (*buf) hipFree(*buf);
-    *buf = nullptr;
-    *bytes = 0;
-    hipError_t e = hipMalloc((void**)buf, need);
-    if (e != hipSuccess) return hip_fail(e, what);
-    *bytes = need;
-    return 0;
+    return queue_preprocess(h, B, Mmax, d_count, d_pose, d_vel, d_plan, delay_mode, d_state, d_coeffs,
+                            (hipStream_t)stream);
 }
 
 int mpcg_rollout_device(mpcg_handle* h, int64_t B, int32_t K, const double* d_courses, const int32_t* d_course_len,
@@ -813,95 +810,79 @@ int mpcg_rollout_device(mpcg_handle* h, int64_t B, int32_t K, const double* d_co
                         double goal_tol, double max_speed, double min_speed, int32_t delay_mode, int32_t integrate,
                         double* d_pose, double* d_vel, int32_t* d_cursor, double* d_ref_v, int32_t* d_done,
                         const mpcg_rollout_logs* logs, void* stream) {
-    if (!h) return fail(-1, "null handle");
-    if (B < 0) return fail(-1, "negative batch");
-    // (every argument error before the first launch: a tick rewrites the robots' state)
+    int rc = batch_check(h, B);
+    if (rc) return rc;
+    // (every refusal before the first launch: a tick rewrites the robots' state)
     if (K < 1) return fail(-1, "K (ticks) must be >= 1");
     int Mmax = 0;
-    int rc = window_args_check(C, Gmax, window_wp, stride, &Mmax);
+    rc = window_args_check(C, Gmax, window_wp, stride, &Mmax);
+    if (rc == 0) rc = params_refusal(h, true);
     if (rc) return rc;
-    rc = mpcg_params_check(&h->params);
-    if (rc) return rc;
-    if (h->params.precision != 0) return fail(-1, kNoFp32Rows);
-    if (!std::isfinite(max_speed) || !std::isfinite(min_speed)) return fail(-1, "max_speed and min_speed must be finite");
+    if (!std::isfinite(max_speed) || !std::isfinite(min_speed)) return fail(-1, kSpeedsFinite);
     if (std::isnan(goal_tol)) return fail(-1, "goal_tol must be a number");
     if (B == 0) return 0;
     if (!d_courses || !d_course_len || !d_course_of || !d_pose || !d_vel || !d_cursor || !d_ref_v || !d_done)
         return fail(-1, "courses, course_len, course_of, pose, vel, cursor, ref_v and done are required");
     hipError_t e = hipSetDevice(h->device);
     if (e != hipSuccess) return hip_fail(e, "hipSetDevice");
-    const size_t uB = (size_t)B;
-    rc = ensure_buffer(h, &h->d_trk, &h->trk_bytes, sizeof(double) * 12 * uB, "hipMalloc(track buffers)");
+    rc = lds_refusal(h);
+    const mpcg::TickLayout L(B, Mmax, 1);
+    if (rc == 0) rc = ensure_tick(h, L, B, 0);
     if (rc) return rc;
-    rc = ensure_buffer(h, &h->d_rows, &h->rows_bytes, sizeof(double) * MPCG_PP_FIELDS * uB, "hipMalloc(parameter rows)");
-    if (rc) return rc;
-    rc = ensure_buffer(h, &h->d_roll, &h->roll_bytes,
-                       sizeof(double) * (2 * (size_t)Mmax + 3) * uB + sizeof(int32_t) * 2 * uB,
-                       "hipMalloc(rollout buffers)");
-    if (rc) return rc;
-    double* st = h->d_trk;
-    double* cf = st + 6 * B;
-    double* u0 = cf + 4 * B;
-    double* plan = h->d_roll;
-    double* cmd = plan + 2 * (size_t)Mmax * uB;
-    int32_t* count = (int32_t*)(cmd + 3 * B);
-    int32_t* start = count + B;
+    double *rows = h->d_tick.at<double>(L.rows), *cmd = h->d_tick.at<double>(L.cmd), *plan = h->d_tick.at<double>(L.plan);
+    int32_t *count = h->d_tick.at<int32_t>(L.count), *start = h->d_tick.at<int32_t>(L.start);
+    const mpcg::PPRow row = mpcg::pp_row_pack(to_ipm(h->params));
+    const mpcg_rollout_logs lg = logs ? *logs : mpcg_rollout_logs{};
+    Tick t{B, Mmax, d_pose, d_vel, plan, count, delay_mode, rows, d_ref_v, cmd, nullptr, nullptr, nullptr};
+    mpcg::RolloutArgs a{};  // (what no tick changes: all but the tick's index and its rows of the logs)
+    a.B = B;
+    a.courses = d_courses;
+    a.course_len = d_course_len;
+    a.course_of = d_course_of;
+    a.C = C;
+    a.Gmax = Gmax;
+    a.goal_tol = goal_tol;
+    a.max_throttle = mpcg::decel_throttle(h->params.max_throttle);
+    a.max_speed = max_speed;
+    a.min_speed = min_speed;
+    a.dt = h->params.dt;
+    a.integrate = integrate ? 1 : 0;
+    a.pose = d_pose;
+    a.vel = d_vel;
+    a.cursor = d_cursor;
+    a.start = start;
+    a.count = count;
+    a.ref_v = d_ref_v;
+    a.done = d_done;
+    a.rows = rows;
+    a.cmd = cmd;
     hipStream_t s = (hipStream_t)stream;
-    rc = order_on(h, s);
-    if (rc) return rc;
-    double row[MPCG_PP_FIELDS];
-    mpcg::pp_row_from(to_ipm(h->params), row);
-    const mpcg_rollout_logs none{};
-    const mpcg_rollout_logs& lg = logs ? *logs : none;
-    for (int32_t k = 0; k < K; ++k) {
-        const size_t o = (size_t)k * uB;  // this tick's row of the logs
-        e = mpcg::launch_plan_window(B, d_courses, d_course_len, d_course_of, C, Gmax, d_pose, window_wp, stride, Mmax,
-                                     d_cursor, plan, count, start, s);
-        if (e != hipSuccess) return hip_fail(e, "plan window launch");
-        mpcg::RolloutArgs a{};
-        a.B = B;
-        a.tick = k;
-        a.courses = d_courses;
-        a.course_len = d_course_len;
-        a.course_of = d_course_of;
-        a.C = C;
-        a.Gmax = Gmax;
-        a.goal_tol = goal_tol;
-        a.max_throttle = mpcg::decel_throttle(h->params.max_throttle);
-        a.max_speed = max_speed;
-        a.min_speed = min_speed;
-        a.dt = h->params.dt;
-        a.integrate = integrate ? 1 : 0;
-        a.pose = d_pose;
-        a.vel = d_vel;
-        a.cursor = d_cursor;
-        a.start = start;
-        a.count = count;
-        a.ref_v = d_ref_v;
-        a.done = d_done;
-        a.rows = h->d_rows;
-        a.cmd = cmd;
-        a.log_pose = lg.pose ? lg.pose + 3 * o : nullptr;
-        a.log_vel = lg.vel ? lg.vel + 3 * o : nullptr;
-        a.log_cmd = lg.cmd ? lg.cmd + 3 * o : nullptr;
-        a.log_ref_v = lg.ref_v ? lg.ref_v + o : nullptr;
-        a.log_cursor = lg.cursor ? lg.cursor + o : nullptr;
-        a.log_start = lg.start ? lg.start + o : nullptr;
-        a.log_count = lg.count ? lg.count + o : nullptr;
-        e = mpcg::launch_rollout_begin(a, row, s);
-        if (e != hipSuccess) return hip_fail(e, "rollout tick launch");
-        e = mpcg::launch_find_best_path_n(B, Mmax, count, h->params.dt, delay_mode ? 1 : 0, d_pose, d_vel, plan, st,
-                                          cf, s);
-        if (e != hipSuccess) return hip_fail(e, "find_best_path launch");
-        rc = solve_device(h, B, st, cf, h->d_rows, u0, nullptr, lg.status ? lg.status + o : nullptr, nullptr,
-                          lg.iters ? lg.iters + o : nullptr, nullptr, stream);
-        if (rc) return rc;
-        e = mpcg::launch_post_pp(B, h->params.dt, d_ref_v, d_vel, u0, cmd, s);
-        if (e != hipSuccess) return hip_fail(e, "post-processing launch");
-        e = mpcg::launch_rollout_end(a, s);
-        if (e != hipSuccess) return hip_fail(e, "rollout tick launch");
-    }
-    return record_on(h, s);
+    return with_scratch(h, s, [&] {
+        for (int32_t k = 0; k < K; ++k) {
+            // this tick's row of a log of w values per robot (null stays null)
+            auto at = [&](auto* log, int w) { return log ? log + (size_t)w * k * (size_t)B : nullptr; };
+            e = mpcg::launch_plan_window(B, d_courses, d_course_len, d_course_of, C, Gmax, d_pose, window_wp, stride,
+                                         Mmax, d_cursor, plan, count, start, s);
+            if (e != hipSuccess) return hip_fail(e, "plan window launch");
+            a.tick = k;
+            a.log_pose = at(lg.pose, 3);
+            a.log_vel = at(lg.vel, 3);
+            a.log_cmd = at(lg.cmd, 3);
+            a.log_ref_v = at(lg.ref_v, 1);
+            a.log_cursor = at(lg.cursor, 1);
+            a.log_start = at(lg.start, 1);
+            a.log_count = at(lg.count, 1);
+            e = mpcg::launch_rollout_begin(a, row, s);
+            if (e != hipSuccess) return hip_fail(e, "rollout tick launch");
+            t.status = at(lg.status, 1);
+            t.iters = at(lg.iters, 1);
+            rc = tick(h, t, L, s);
+            if (rc) return rc;
+            e = mpcg::launch_rollout_end(a, s);
+            if (e != hipSuccess) return hip_fail(e, "rollout tick launch");
+        }
+        return 0;
+    });
 }
 
 const char* mpcg_last_kernel(const mpcg_handle* h) { return h ? h->last_kernel : ""; }

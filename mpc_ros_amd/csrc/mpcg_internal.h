@@ -43,21 +43,23 @@ size_t wide_sched_bytes(int64_t B);
 hipError_t launch_wide_order(int64_t B, const double* coeffs, void* buf, size_t bytes, int32_t** order,
                              hipStream_t stream);
 
-// findBestPath preprocessing and post-processing (mpcg_track.hip).
-// (M > 64: ws holds find_best_path_ws_bytes(B, M) bytes of device scratch)
+// A control tick's lane kernels (mpcg_track.hip; the pipeline is mpcg_api.cpp tick).
+// findBestPath's preprocessing: count null -- M waypoints for every robot (M > 64: ws holds
+// find_best_path_ws_bytes(B, M) bytes of device scratch); else count[p] waypoints for robot p in
+// plan rows of M (<= 64).
 size_t find_best_path_ws_bytes(int64_t B, int M);
-hipError_t launch_find_best_path(int64_t B, int M, double dt, int delay_mode, const double* pose, const double* vel,
-                                 const double* plan, double* state, double* coeffs, double* ws, hipStream_t stream);
-hipError_t launch_post(int64_t B, double dt, double ref_v, const double* vel, const double* u0, double* cmd,
-                       hipStream_t stream);
+hipError_t launch_find_best_path(int64_t B, int M, const int32_t* count, double dt, int delay_mode, const double* pose,
+                                 const double* vel, const double* plan, double* state, double* coeffs, double* ws,
+                                 hipStream_t stream);
+// the post-processing: the speed clamp is ref_v, or the robot's own ref_vs[b] where ref_vs is given
+hipError_t launch_post(int64_t B, double dt, double ref_v, const double* ref_vs, const double* vel, const double* u0,
+                       double* cmd, hipStream_t stream);
 // The tick with a goal per robot (mpcg_track_device_goal): Tracking::deceleration on ref_v [B]
-// (in/out) and each robot's parameter row -- `row`'s 16 doubles with REF_V = ref_v[b] -- into
-// rows [B][16]; the post-processing with the robot's own REF_V.
+// (in/out) and each robot's parameter row -- `row` with REF_V = ref_v[b] -- into rows [B][16].
+struct PPRow;
 hipError_t launch_decelerate(int64_t B, const double* pose, const double* vel, const double* goal, double* ref_v,
-                             double max_throttle, double max_speed, double min_speed, const double* row, double* rows,
+                             double max_throttle, double max_speed, double min_speed, const PPRow& row, double* rows,
                              hipStream_t stream);
-hipError_t launch_post_pp(int64_t B, double dt, const double* ref_v, const double* vel, const double* u0, double* cmd,
-                          hipStream_t stream);
 
 // The closed loop on the device (mpcg_track.hip; the window rule is mpcg_window.h).
 // The plan window of B robots on C shared courses [C][Gmax][2]: cursor [B] in/out, plan
@@ -65,10 +67,6 @@ hipError_t launch_post_pp(int64_t B, double dt, const double* ref_v, const doubl
 hipError_t launch_plan_window(int64_t B, const double* courses, const int32_t* course_len, const int32_t* course_of,
                               int C, int Gmax, const double* pose, int window_wp, int stride, int Mmax,
                               int32_t* cursor, double* plan, int32_t* count, int32_t* start, hipStream_t stream);
-// launch_find_best_path with count[p] waypoints for robot p in plan rows of Mmax (<= 64)
-hipError_t launch_find_best_path_n(int64_t B, int Mmax, const int32_t* count, double dt, int delay_mode,
-                                   const double* pose, const double* vel, const double* plan, double* state,
-                                   double* coeffs, hipStream_t stream);
 // One rollout tick around the solve.  begin, after the window: Tracking::deceleration towards
 // the goal (the course's last waypoint), the done mark, the robot's parameter row (`row` with
 // REF_V = ref_v[b]; a done robot's is invalid) and the tick's inputs into the logs.  end, after
@@ -96,7 +94,7 @@ struct RolloutArgs {
     double *log_pose, *log_vel, *log_cmd, *log_ref_v;
     int32_t *log_cursor, *log_start, *log_count;
 };
-hipError_t launch_rollout_begin(const RolloutArgs& a, const double* row, hipStream_t stream);
+hipError_t launch_rollout_begin(const RolloutArgs& a, const PPRow& row, hipStream_t stream);
 hipError_t launch_rollout_end(const RolloutArgs& a, hipStream_t stream);
 
 // The benchmark's synthetic robots (mpcg_synth.hip): the lemniscate's arc-length table (host,

@@ -1,7 +1,8 @@
 // mpc_ros_amd/csrc/mpcg_pp.h -- per-problem parameter rows (include/mpcg.h MPCG_PP_*): a row's
-// domain check and its fields as IpmParams, and Tracking::deceleration's rule.  Host and device:
-// mpcg_api.cpp (mpcg_pparams_check, mpcg_decelerate) and the kernels (k_solve_wide_pp,
-// k_resume_wide_pp, k_decelerate) run the same code.
+// domain check and its fields as IpmParams, a row by value (PPRow) and a robot's row written from
+// the handle's, and Tracking::deceleration's rule.  Host and device: mpcg_api.cpp
+// (mpcg_pparams_check, mpcg_decelerate) and the kernels (k_solve_wide_pp, k_resume_wide_pp,
+// k_decelerate, k_rollout_begin) run the same code.
 #ifndef MPCG_PP_H
 #define MPCG_PP_H
 
@@ -62,6 +63,24 @@ MPCG_HD void pp_row_from(const IpmParams& P, double* r) {
     r[MPCG_PP_BOUND] = P.bound;
     r[MPCG_PP_LF] = P.lf;
     r[MPCG_PP_RESERVED] = 0.0;
+}
+
+// A row by value: a kernel argument (the handle's row, pp_row_pack) or a problem's row in
+// registers (mpcg_wide_kern.h pp_load_row)
+struct PPRow {
+    double f[MPCG_PP_FIELDS];
+};
+MPCG_HD PPRow pp_row_pack(const IpmParams& P) {
+    PPRow r;
+    pp_row_from(P, r.f);
+    return r;
+}
+// a robot's row r[16]: `row` with REF_V = ref_v; !valid: an invalid row (DT = 0), which the
+// solve's row validation ends at iteration 0 with status 13 and zero controls
+MPCG_HD void pp_row_write(const PPRow& row, double ref_v, bool valid, double* r) {
+#pragma unroll
+    for (int j = 0; j < MPCG_PP_FIELDS; ++j)
+        r[j] = j == MPCG_PP_REF_V ? ref_v : (j == MPCG_PP_DT && !valid) ? 0.0 : row.f[j];
 }
 
 // Tracking::deceleration (driving_state.cpp:121-141), the quirk kept: the first branch sets

@@ -7,12 +7,19 @@
 //   first int(0.3 M) waypoint increments (:214-235), delay-mode state prediction
 //   (:242-256);
 // and the post-processing of the solve (:262-269): w = w0, throttle = a0,
-// speed = min(v_fb + throttle dt, REF_V).  For the tick with a goal per robot
-// (mpcg_track_device_goal) also Tracking::deceleration (:121-141, k_decelerate: each robot's
-// REF_V and parameter row) and the post-processing with the robot's own REF_V (k_post_pp).
-// For the closed loop on the device (mpcg_rollout_device): the plan window from a shared course
-// (k_plan_window, the rule of mpcg_window.h), the preprocessing with a waypoint count per robot
-// (k_find_best_path_n) and the two ends of a rollout tick (k_rollout_begin, k_rollout_end).
+// speed = min(v_fb + throttle dt, REF_V).
+//
+// Every control tick is one pipeline (mpcg_api.cpp tick): preprocessing, solve, post-processing.
+//   preprocessing   k_find_best_path<16|64> / k_find_best_path_long: M waypoints for every robot;
+//                   k_find_best_path_n<16|64>: a count per robot in plan rows of M <= 64.  One
+//                   body, find_best_path_pass.
+//   post-processing k_post: the clamp to the handle's REF_V or to the robot's own.
+// mpcg_track_device is the tick alone.  mpcg_track_device_goal runs k_decelerate before it
+// (Tracking::deceleration, :121-141: each robot's REF_V and its parameter row, pp_row_write).
+// mpcg_rollout_device runs per tick k_plan_window (the plan window from a shared course, the rule
+// of mpcg_window.h) and k_rollout_begin (deceleration, the done mark, the row, the logs) before
+// it and k_rollout_end (the unicycle, the command's log) after it.  Every launch goes through
+// launch_lanes.
 //
 // The QR runs on MAXM-row arrays (the M waypoint rows followed by zero rows, which
 // change no norm or inner product), unrolled so they stay in registers for M <= 16;
@@ -95,14 +102,13 @@ struct TrackArgs {
 __device__ __forceinline__ void finish_state(const TrackArgs& a, int64_t p, double theta, double v, double w,
                                              double throttle, const double* c);
 
+// findBestPath's preprocessing of robot p on a.M waypoints: the body of k_find_best_path, and one
+// pass of k_find_best_path_n
 template <int MAXM>
-__global__ void __launch_bounds__(64) k_find_best_path(TrackArgs a) {
-    const int64_t p = (int64_t)blockIdx.x * 64 + threadIdx.x;
-    if (p >= a.B) return;
+__device__ __forceinline__ void find_best_path_pass(const TrackArgs& a, int64_t p) {
     const int M = a.M;
     const double px = a.pose[p * 3 + 0], py = a.pose[p * 3 + 1], theta = a.pose[p * 3 + 2];
     const double v = a.vel[p * 3 + 0], w = a.vel[p * 3 + 1], throttle = a.vel[p * 3 + 2];
-    const double dt = a.dt;
     const double* pl = a.plan + p * (int64_t)M * 2;
     const double ct = cos(theta), st = sin(theta);
     double xv[MAXM], yv[MAXM];
@@ -119,6 +125,13 @@ __global__ void __launch_bounds__(64) k_find_best_path(TrackArgs a) {
     double c[4];
     polyfit3<MAXM>(M, xv, yv, c);
     finish_state(a, p, theta, v, w, throttle, c);
+}
+
+template <int MAXM>
+__global__ void __launch_bounds__(64) k_find_best_path(TrackArgs a) {
+    const int64_t p = (int64_t)blockIdx.x * 64 + threadIdx.x;
+    if (p >= a.B) return;
+    find_best_path_pass<MAXM>(a, p);
 }
 
 // Plans of more than 64 waypoints: polyfit3's Householder QR, same operations in the same
@@ -225,11 +238,13 @@ __device__ __forceinline__ void finish_state(const TrackArgs& a, int64_t p, doub
     co[3] = c[3];
 }
 
-// driving_state.cpp:262-269 -> cmd[B][3] = (speed, w, throttle)
-__global__ void __launch_bounds__(64) k_post(int64_t B, double dt, double ref_v, const double* vel, const double* u0,
-                                            double* cmd) {
+// driving_state.cpp:262-269 -> cmd[B][3] = (speed, w, throttle).  The clamp is REF_V: ref_v, or
+// the robot's own ref_vs[p] where ref_vs is given (:267-268 reads the map's current entry)
+__global__ void __launch_bounds__(64) k_post(int64_t B, double dt, double ref_v, const double* ref_vs,
+                                            const double* vel, const double* u0, double* cmd) {
     const int64_t p = (int64_t)blockIdx.x * 64 + threadIdx.x;
     if (p >= B) return;
+    if (ref_vs) ref_v = ref_vs[p];
     const double w = u0[p * 2 + 0], thr = u0[p * 2 + 1];
     double speed = vel[p * 3 + 0] + thr * dt;
     if (speed >= ref_v) speed = ref_v;
@@ -264,34 +279,16 @@ __device__ __forceinline__ double hypot_cr(double x, double y) {
 
 // Tracking::deceleration (driving_state.cpp:121-141) for B robots, one per lane: ref_v[b] (in/out,
 // the robot's REF_V map entry) from its distance to its goal and its feedback speed, then the
-// robot's parameter row: the handle's row with REF_V = ref_v[b].
-struct PRow {
-    double f[MPCG_PP_FIELDS];
-};
+// robot's parameter row: the handle's row with REF_V = ref_v[b] (pp_row_write).
 __global__ void __launch_bounds__(64) k_decelerate(int64_t B, const double* pose, const double* vel, const double* goal,
                                                   double* ref_v, double max_throttle, double max_speed,
-                                                  double min_speed, PRow row, double* rows) {
+                                                  double min_speed, PPRow row, double* rows) {
     const int64_t p = (int64_t)blockIdx.x * 64 + threadIdx.x;
     if (p >= B) return;
     const double dist = hypot_cr(pose[p * 3 + 0] - goal[p * 2 + 0], pose[p * 3 + 1] - goal[p * 2 + 1]);
     const double rv = decelerate(dist, vel[p * 3 + 0], max_throttle, max_speed, min_speed, ref_v[p]);
     ref_v[p] = rv;
-    double* r = rows + p * MPCG_PP_FIELDS;
-#pragma unroll
-    for (int j = 0; j < MPCG_PP_FIELDS; ++j) r[j] = j == MPCG_PP_REF_V ? rv : row.f[j];
-}
-
-// driving_state.cpp:262-269 with the robot's own REF_V (:267-268 reads the map's current entry)
-__global__ void __launch_bounds__(64) k_post_pp(int64_t B, double dt, const double* ref_v, const double* vel,
-                                               const double* u0, double* cmd) {
-    const int64_t p = (int64_t)blockIdx.x * 64 + threadIdx.x;
-    if (p >= B) return;
-    const double w = u0[p * 2 + 0], thr = u0[p * 2 + 1];
-    double speed = vel[p * 3 + 0] + thr * dt;
-    if (speed >= ref_v[p]) speed = ref_v[p];
-    cmd[p * 3 + 0] = speed;
-    cmd[p * 3 + 1] = w;
-    cmd[p * 3 + 2] = thr;
+    pp_row_write(row, rv, true, rows + p * MPCG_PP_FIELDS);
 }
 
 // ---- The closed loop on the device (mpcg_rollout_device): the plan window from a shared course,
@@ -347,33 +344,9 @@ __global__ void __launch_bounds__(64) k_plan_window(WindowArgs a) {
 // fitted: its state and coeffs are 0.
 // The wavefront makes one pass per distinct count among its robots, the count wave-uniform in
 // each (the first waiting lane's; the lanes that hold it run the pass): the pass is
-// k_find_best_path's code on a scalar M, so a robot's result does not depend on its neighbours'
-// counts, and a batch of one count is that kernel's arithmetic.  Most robots of a fleet hold a
-// full window, so a wavefront makes one to three passes.
-// (k_find_best_path's body, statement for statement, for one robot)
-template <int MAXM>
-__device__ __forceinline__ void find_best_path_pass(const TrackArgs& a, int64_t p) {
-    const int M = a.M;
-    const double px = a.pose[p * 3 + 0], py = a.pose[p * 3 + 1], theta = a.pose[p * 3 + 2];
-    const double v = a.vel[p * 3 + 0], w = a.vel[p * 3 + 1], throttle = a.vel[p * 3 + 2];
-    const double* pl = a.plan + p * (int64_t)M * 2;
-    const double ct = cos(theta), st = sin(theta);
-    double xv[MAXM], yv[MAXM];
-#pragma unroll
-    for (int i = 0; i < MAXM; ++i) {
-        double dx = 0, dy = 0;
-        if (i < M) {
-            dx = pl[2 * i] - px;
-            dy = pl[2 * i + 1] - py;
-        }
-        xv[i] = dx * ct + dy * st;
-        yv[i] = dy * ct - dx * st;
-    }
-    double c[4];
-    polyfit3<MAXM>(M, xv, yv, c);
-    finish_state(a, p, theta, v, w, throttle, c);
-}
-
+// k_find_best_path's body (find_best_path_pass) on a scalar M, so a robot's result does not
+// depend on its neighbours' counts, and a batch of one count is that kernel's arithmetic.  Most
+// robots of a fleet hold a full window, so a wavefront makes one to three passes.
 template <int MAXM>
 __global__ void __launch_bounds__(64) k_find_best_path_n(TrackArgs a, const int32_t* count) {
     const int64_t p = (int64_t)blockIdx.x * 64 + threadIdx.x;
@@ -409,7 +382,7 @@ __global__ void __launch_bounds__(64) k_find_best_path_n(TrackArgs a, const int3
 // robot is 0; the unicycle over one control period; the command into the log.
 // (RolloutArgs: mpcg_internal.h)
 
-__global__ void __launch_bounds__(64) k_rollout_begin(RolloutArgs a, PRow row) {
+__global__ void __launch_bounds__(64) k_rollout_begin(RolloutArgs a, PPRow row) {
     const int64_t p = (int64_t)blockIdx.x * 64 + threadIdx.x;
     if (p >= a.B) return;
     int G = 0;
@@ -429,12 +402,8 @@ __global__ void __launch_bounds__(64) k_rollout_begin(RolloutArgs a, PRow row) {
         dn = a.tick + 1;
         a.done[p] = dn;
     }
-    // a done robot's row is invalid (DT = 0): the solve's row validation ends its problem at
-    // iteration 0 with status 13 and zero controls
-    double* r = a.rows + p * MPCG_PP_FIELDS;
-#pragma unroll
-    for (int j = 0; j < MPCG_PP_FIELDS; ++j)
-        r[j] = j == MPCG_PP_REF_V ? rv : (j == MPCG_PP_DT && dn != 0) ? 0.0 : row.f[j];
+    // (a done robot's row is invalid: its problem ends at iteration 0 with zero controls)
+    pp_row_write(row, rv, dn == 0, a.rows + p * MPCG_PP_FIELDS);
     if (a.log_pose)
         for (int j = 0; j < 3; ++j) a.log_pose[p * 3 + j] = a.pose[p * 3 + j];
     if (a.log_vel)
@@ -470,86 +439,57 @@ __global__ void __launch_bounds__(64) k_rollout_end(RolloutArgs a) {
     a.vel[p * 3 + 2] = thr;
 }
 
-static dim3 lane_grid(int64_t B) { return dim3((unsigned)((B + 63) / 64)); }
+// the launch of every kernel here: one robot per lane, 64 per workgroup; nothing for no robots
+template <class Kernel, class... Args>
+static hipError_t launch_lanes(Kernel kernel, int64_t B, hipStream_t stream, const Args&... args) {
+    if (B <= 0) return hipSuccess;
+    hipLaunchKernelGGL(kernel, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, stream, args...);
+    return hipGetLastError();
+}
 
 hipError_t launch_plan_window(int64_t B, const double* courses, const int32_t* course_len, const int32_t* course_of,
                               int C, int Gmax, const double* pose, int window_wp, int stride, int Mmax,
                               int32_t* cursor, double* plan, int32_t* count, int32_t* start, hipStream_t stream) {
-    if (B <= 0) return hipSuccess;
     const WindowArgs a{B, courses, course_len, course_of, C, Gmax, pose, window_wp, stride, Mmax, cursor, plan, count,
                        start};
-    hipLaunchKernelGGL(k_plan_window, lane_grid(B), dim3(64), 0, stream, a);
-    return hipGetLastError();
-}
-
-hipError_t launch_find_best_path_n(int64_t B, int Mmax, const int32_t* count, double dt, int delay_mode,
-                                   const double* pose, const double* vel, const double* plan, double* state,
-                                   double* coeffs, hipStream_t stream) {
-    if (B <= 0) return hipSuccess;
-    if (Mmax > kWindowMaxM) return hipErrorInvalidValue;
-    const TrackArgs a{B, Mmax, dt, delay_mode, pose, vel, plan, state, coeffs};
-    if (Mmax <= 16)
-        hipLaunchKernelGGL(k_find_best_path_n<16>, lane_grid(B), dim3(64), 0, stream, a, count);
-    else
-        hipLaunchKernelGGL(k_find_best_path_n<64>, lane_grid(B), dim3(64), 0, stream, a, count);
-    return hipGetLastError();
-}
-
-hipError_t launch_rollout_begin(const RolloutArgs& a, const double* row, hipStream_t stream) {
-    if (a.B <= 0) return hipSuccess;
-    PRow r;
-    for (int j = 0; j < MPCG_PP_FIELDS; ++j) r.f[j] = row[j];
-    hipLaunchKernelGGL(k_rollout_begin, lane_grid(a.B), dim3(64), 0, stream, a, r);
-    return hipGetLastError();
-}
-
-hipError_t launch_rollout_end(const RolloutArgs& a, hipStream_t stream) {
-    if (a.B <= 0) return hipSuccess;
-    hipLaunchKernelGGL(k_rollout_end, lane_grid(a.B), dim3(64), 0, stream, a);
-    return hipGetLastError();
-}
-
-hipError_t launch_decelerate(int64_t B, const double* pose, const double* vel, const double* goal, double* ref_v,
-                             double max_throttle, double max_speed, double min_speed, const double* row, double* rows,
-                             hipStream_t stream) {
-    if (B <= 0) return hipSuccess;
-    PRow r;
-    for (int j = 0; j < MPCG_PP_FIELDS; ++j) r.f[j] = row[j];
-    hipLaunchKernelGGL(k_decelerate, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, stream, B, pose, vel, goal, ref_v,
-                       max_throttle, max_speed, min_speed, r, rows);
-    return hipGetLastError();
-}
-
-hipError_t launch_post_pp(int64_t B, double dt, const double* ref_v, const double* vel, const double* u0, double* cmd,
-                          hipStream_t stream) {
-    if (B <= 0) return hipSuccess;
-    hipLaunchKernelGGL(k_post_pp, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, stream, B, dt, ref_v, vel, u0, cmd);
-    return hipGetLastError();
-}
-
-hipError_t launch_find_best_path(int64_t B, int M, double dt, int delay_mode, const double* pose, const double* vel,
-                                 const double* plan, double* state, double* coeffs, double* ws, hipStream_t stream) {
-    if (B <= 0) return hipSuccess;
-    const TrackArgs a{B, M, dt, delay_mode, pose, vel, plan, state, coeffs};
-    const dim3 grid((unsigned)((B + 63) / 64)), block(64);
-    if (M <= 16)
-        hipLaunchKernelGGL(k_find_best_path<16>, grid, block, 0, stream, a);
-    else if (M <= 64)
-        hipLaunchKernelGGL(k_find_best_path<64>, grid, block, 0, stream, a);
-    else if (!ws)
-        return hipErrorInvalidValue;
-    else
-        hipLaunchKernelGGL(k_find_best_path_long, grid, block, 0, stream, a, ws);
-    return hipGetLastError();
+    return launch_lanes(k_plan_window, B, stream, a);
 }
 
 size_t find_best_path_ws_bytes(int64_t B, int M) { return M > 64 ? sizeof(double) * 6 * (size_t)M * (size_t)B : 0; }
 
-hipError_t launch_post(int64_t B, double dt, double ref_v, const double* vel, const double* u0, double* cmd,
-                       hipStream_t stream) {
-    if (B <= 0) return hipSuccess;
-    hipLaunchKernelGGL(k_post, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, stream, B, dt, ref_v, vel, u0, cmd);
-    return hipGetLastError();
+hipError_t launch_find_best_path(int64_t B, int M, const int32_t* count, double dt, int delay_mode, const double* pose,
+                                 const double* vel, const double* plan, double* state, double* coeffs, double* ws,
+                                 hipStream_t stream) {
+    const TrackArgs a{B, M, dt, delay_mode, pose, vel, plan, state, coeffs};
+    if (count) {
+        if (M > kWindowMaxM) return hipErrorInvalidValue;
+        return M <= 16 ? launch_lanes(k_find_best_path_n<16>, B, stream, a, count)
+                       : launch_lanes(k_find_best_path_n<64>, B, stream, a, count);
+    }
+    if (M <= 16) return launch_lanes(k_find_best_path<16>, B, stream, a);
+    if (M <= 64) return launch_lanes(k_find_best_path<64>, B, stream, a);
+    if (!ws) return hipErrorInvalidValue;
+    return launch_lanes(k_find_best_path_long, B, stream, a, ws);
+}
+
+hipError_t launch_post(int64_t B, double dt, double ref_v, const double* ref_vs, const double* vel, const double* u0,
+                       double* cmd, hipStream_t stream) {
+    return launch_lanes(k_post, B, stream, B, dt, ref_v, ref_vs, vel, u0, cmd);
+}
+
+hipError_t launch_decelerate(int64_t B, const double* pose, const double* vel, const double* goal, double* ref_v,
+                             double max_throttle, double max_speed, double min_speed, const PPRow& row, double* rows,
+                             hipStream_t stream) {
+    return launch_lanes(k_decelerate, B, stream, B, pose, vel, goal, ref_v, max_throttle, max_speed, min_speed, row,
+                        rows);
+}
+
+hipError_t launch_rollout_begin(const RolloutArgs& a, const PPRow& row, hipStream_t stream) {
+    return launch_lanes(k_rollout_begin, a.B, stream, a, row);
+}
+
+hipError_t launch_rollout_end(const RolloutArgs& a, hipStream_t stream) {
+    return launch_lanes(k_rollout_end, a.B, stream, a);
 }
 
 }  // namespace mpcg

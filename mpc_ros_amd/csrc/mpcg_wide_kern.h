@@ -158,10 +158,7 @@ __device__ __forceinline__ void write_out(const WideArgs& a, Solver& S, int64_t 
 // through the solve; otherwise (the resume kernel) they stay wave-uniform and the allocator holds
 // them in SGPRs and SGPR spill slots.  Held in VGPRs the batch kernel measured 0.8-2.7 % faster
 // in every horizon class timed, also where it then spills 5-18 VGPRs (DESIGN.md "Per-problem
-// parameters").
-struct PPRow {
-    double f[MPCG_PP_FIELDS];
-};
+// parameters").  (PPRow: mpcg_pp.h)
 template <bool VHOLD = false>
 __device__ __forceinline__ PPRow pp_load_row(const double* pparams, int64_t p) {
     typedef const double __attribute__((address_space(4))) cdouble;

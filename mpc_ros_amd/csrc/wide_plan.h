@@ -1,6 +1,7 @@
 // mpc_ros_amd/csrc/wide_plan.h -- the launch plan of the wavefront solver (mpcg_wide.hip), as
 // plain arithmetic on (IpmParams, B, slot budget, XCD count): the kernel instances the library
-// carries and the choice among them, and the layout of the HBM workspace.  No GPU runtime: the
+// carries and the choice among them, the layout of the HBM workspace, and the layout of a control
+// tick's scratch (TickLayout: plain arithmetic on (B, Mmax, rows)).  No GPU runtime: the
 // launch side passes in what only the runtime can say (the occupancy behind the slot budget,
 // the XCD count), and tests/native/wide_plan_check.cpp checks all of it on the host.
 #ifndef MPCG_WIDE_PLAN_H
@@ -327,6 +328,35 @@ struct SolveLayout {
             head = PhaseLayout(Ph, head_n, budget(Ph, head_n), nxcc);
             total = head_off + head.total;
         }
+    }
+};
+
+// ---------------------------------------------------------------- the tick scratch
+// The intermediates of one control tick of B robots (mpcg_api.cpp tick), one handle buffer:
+// state [B][6] | coeffs [B][4] | u0 [B][2] | the robots' parameter rows [B][16] (rows != 0: the
+// tick with a goal, the rollout) | and for the rollout (Mmax > 0: its plan rows per robot) cmd
+// [B][3] | the windows' plans [B][Mmax][2] | count [B] | start [B].  Doubles first, the two int32
+// regions last; every region from an 8-byte boundary.  Nothing in it outlives a call, so the
+// layout may differ from one call to the next.
+constexpr int kRowFields = 16;  // (MPCG_PP_FIELDS of include/mpcg.h, which this header does not need)
+struct TickLayout {
+    Region state, coeffs, u0, rows, cmd, plan, count, start;
+    size_t total = 0;
+    TickLayout(int64_t B, int Mmax, int rows_) {
+        const size_t b = (size_t)B, roll = Mmax > 0 ? b : 0;
+        auto take = [this](size_t bytes) {
+            const Region r{total, round_up(bytes, 8)};
+            total += r.bytes;
+            return r;
+        };
+        state = take(sizeof(double) * 6 * b);
+        coeffs = take(sizeof(double) * 4 * b);
+        u0 = take(sizeof(double) * 2 * b);
+        rows = take(rows_ ? sizeof(double) * kRowFields * b : 0);
+        cmd = take(sizeof(double) * 3 * roll);
+        plan = take(sizeof(double) * 2 * (size_t)Mmax * roll);
+        count = take(sizeof(int32_t) * roll);
+        start = take(sizeof(int32_t) * roll);
     }
 };
 

@@ -65,6 +65,26 @@ def _host_batch(state, coeffs, N, want_traj=True, diag=False):
     return B, out, ptrs
 
 
+def _on_device(t, shape, dtype="float64"):
+    """t is a contiguous torch tensor of this dtype and shape on a GPU."""
+    import torch
+
+    assert t.is_cuda and t.dtype == getattr(torch, dtype) and t.is_contiguous() and tuple(t.shape) == tuple(shape)
+
+
+def _ptr(t):
+    return C.c_void_p(t.data_ptr()) if t is not None else None
+
+
+def _stream_ptr(stream, like):
+    """The stream's handle for the C-ABI (None: torch's current stream on `like`'s device)."""
+    import torch
+
+    if stream is None:
+        stream = torch.cuda.current_stream(like.device)
+    return C.c_void_p(stream.cuda_stream)
+
+
 class BatchSolver:
     def __init__(self, device: int = 0, params: dict | None = None, strategy: str = "wave", dtype: str = "fp64",
                  **ipopt):
@@ -155,27 +175,23 @@ class BatchSolver:
         import torch
 
         B = state.shape[0]
-        for t, shape, dt in ((state, (B, 6), torch.float64), (coeffs, (B, 4), torch.float64),
-                             (u0, (B, 2), torch.float64)):
-            assert t.is_cuda and t.dtype == dt and t.is_contiguous() and tuple(t.shape) == shape
+        for t, shape in ((state, (B, 6)), (coeffs, (B, 4)), (u0, (B, 2))):
+            _on_device(t, shape)
         if traj is not None:
             assert traj.dtype == torch.float64 and traj.is_contiguous() and traj.numel() == B * 3 * self.N
         for t in (status, iters):
             assert t is None or (t.dtype == torch.int32 and t.numel() == B)
         assert diag is None or (diag.dtype == torch.int32 and diag.numel() == 4 * B and diag.is_contiguous())
-        if stream is None:
-            stream = torch.cuda.current_stream(state.device)
-        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None  # noqa: E731
+        ptr, sp = _ptr, _stream_ptr(stream, state)
         if pparams is not None:
-            assert (pparams.is_cuda and pparams.dtype == torch.float64 and pparams.is_contiguous()
-                    and tuple(pparams.shape) == (B, _lib.PP_FIELDS))
+            _on_device(pparams, (B, _lib.PP_FIELDS))
             _lib.check(_lib.lib().mpcg_solve_device_pp(
                 self._h, B, ptr(state), ptr(coeffs), ptr(pparams), ptr(u0), ptr(traj), ptr(status), ptr(obj),
-                ptr(iters), ptr(diag), C.c_void_p(stream.cuda_stream)), "mpcg_solve_device_pp")
+                ptr(iters), ptr(diag), sp), "mpcg_solve_device_pp")
             return
         _lib.check(_lib.lib().mpcg_solve_device_ex(
             self._h, B, ptr(state), ptr(coeffs), ptr(u0), ptr(traj), ptr(status), ptr(obj), ptr(iters), ptr(diag),
-            C.c_void_p(stream.cuda_stream)), "mpcg_solve_device_ex")
+            sp), "mpcg_solve_device_ex")
 
     # ------------------------------------------------ the benchmark's synthetic robots
     def synth_infinity_device(self, start: int, B: int, M: int = 11, seed: int | None = None, stream=None):
@@ -189,12 +205,9 @@ class BatchSolver:
         pose = torch.empty((B, 3), dtype=torch.float64, device=dev)
         vel = torch.empty((B, 3), dtype=torch.float64, device=dev)
         plan = torch.empty((B, M, 2), dtype=torch.float64, device=dev)
-        if stream is None:
-            stream = torch.cuda.current_stream(dev)
         _lib.check(_lib.lib().mpcg_synth_infinity_device(
-            self._h, int(infinity.SEED if seed is None else seed), int(start), int(B), int(M), C.c_void_p(pose.data_ptr()),
-            C.c_void_p(vel.data_ptr()), C.c_void_p(plan.data_ptr()), C.c_void_p(stream.cuda_stream)),
-            "mpcg_synth_infinity_device")
+            self._h, int(infinity.SEED if seed is None else seed), int(start), int(B), int(M), _ptr(pose), _ptr(vel),
+            _ptr(plan), _stream_ptr(stream, pose)), "mpcg_synth_infinity_device")
         return pose, vel, plan
 
     # ------------------------------------------------ the caller side on the device
@@ -205,23 +218,19 @@ class BatchSolver:
         plan [B,M,2] -> state [B,6], coeffs [B,4]; torch float64 tensors on this GPU.
         count [B] int32: robot p's own waypoint count in its M <= 64 plan rows
         (mpcg_preprocess_device_n); a robot with count < 4 is not fitted, its outputs are 0."""
-        import torch
-
         B, M = plan.shape[0], plan.shape[1]
         for t, shape in ((pose, (B, 3)), (vel, (B, 3)), (plan, (B, M, 2)), (state, (B, 6)), (coeffs, (B, 4))):
-            assert t.is_cuda and t.dtype == torch.float64 and t.is_contiguous() and tuple(t.shape) == shape
-        if stream is None:
-            stream = torch.cuda.current_stream(pose.device)
-        ptr = lambda t: C.c_void_p(t.data_ptr())  # noqa: E731
+            _on_device(t, shape)
+        ptr, sp = _ptr, _stream_ptr(stream, pose)
         if count is not None:
-            assert count.is_cuda and count.dtype == torch.int32 and count.is_contiguous() and tuple(count.shape) == (B,)
+            _on_device(count, (B,), "int32")
             _lib.check(_lib.lib().mpcg_preprocess_device_n(
                 self._h, B, M, ptr(pose), ptr(vel), ptr(plan), ptr(count), int(bool(delay_mode)), ptr(state),
-                ptr(coeffs), C.c_void_p(stream.cuda_stream)), "mpcg_preprocess_device_n")
+                ptr(coeffs), sp), "mpcg_preprocess_device_n")
             return
         _lib.check(_lib.lib().mpcg_preprocess_device(
-            self._h, B, M, ptr(pose), ptr(vel), ptr(plan), int(bool(delay_mode)), ptr(state), ptr(coeffs),
-            C.c_void_p(stream.cuda_stream)), "mpcg_preprocess_device")
+            self._h, B, M, ptr(pose), ptr(vel), ptr(plan), int(bool(delay_mode)), ptr(state), ptr(coeffs), sp),
+            "mpcg_preprocess_device")
 
     def track_device(self, pose, vel, plan, cmd, traj=None, status=None, delay_mode: bool = True, stream=None,
                      goal=None, ref_v=None, max_speed: float = 0.7, min_speed: float = 0.05):
@@ -236,37 +245,31 @@ class BatchSolver:
 
         B, M = plan.shape[0], plan.shape[1]
         for t, shape in ((pose, (B, 3)), (vel, (B, 3)), (plan, (B, M, 2)), (cmd, (B, 3))):
-            assert t.is_cuda and t.dtype == torch.float64 and t.is_contiguous() and tuple(t.shape) == shape
+            _on_device(t, shape)
         if traj is not None:
             assert traj.dtype == torch.float64 and traj.is_contiguous() and traj.numel() == B * 3 * self.N
         assert status is None or (status.dtype == torch.int32 and status.numel() == B)
-        if stream is None:
-            stream = torch.cuda.current_stream(pose.device)
-        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None  # noqa: E731
+        ptr, sp = _ptr, _stream_ptr(stream, pose)
         if (goal is None) != (ref_v is None):
             raise ValueError("goal and ref_v go together")
         if goal is not None:
-            for t, shape in ((goal, (B, 2)), (ref_v, (B,))):
-                assert t.is_cuda and t.dtype == torch.float64 and t.is_contiguous() and tuple(t.shape) == shape
+            _on_device(goal, (B, 2))
+            _on_device(ref_v, (B,))
             _lib.check(_lib.lib().mpcg_track_device_goal(
                 self._h, B, M, ptr(pose), ptr(vel), ptr(plan), ptr(goal), ptr(ref_v), float(max_speed), float(min_speed),
-                int(bool(delay_mode)), ptr(cmd), ptr(traj), ptr(status), C.c_void_p(stream.cuda_stream)),
-                "mpcg_track_device_goal")
+                int(bool(delay_mode)), ptr(cmd), ptr(traj), ptr(status), sp), "mpcg_track_device_goal")
             return
         _lib.check(_lib.lib().mpcg_track_device(
-            self._h, B, M, ptr(pose), ptr(vel), ptr(plan), int(bool(delay_mode)), ptr(cmd), ptr(traj), ptr(status),
-            C.c_void_p(stream.cuda_stream)), "mpcg_track_device")
+            self._h, B, M, ptr(pose), ptr(vel), ptr(plan), int(bool(delay_mode)), ptr(cmd), ptr(traj), ptr(status), sp),
+            "mpcg_track_device")
 
     # ------------------------------------------------ the closed loop on the device
     @staticmethod
     def _courses(courses, course_len, course_of, B):
-        import torch
-
         Cn, Gmax = courses.shape[0], courses.shape[1]
-        assert courses.is_cuda and courses.dtype == torch.float64 and courses.is_contiguous()
-        assert tuple(courses.shape) == (Cn, Gmax, 2)
-        for t, n in ((course_len, Cn), (course_of, B)):
-            assert t.is_cuda and t.dtype == torch.int32 and t.is_contiguous() and tuple(t.shape) == (n,)
+        _on_device(courses, (Cn, Gmax, 2))
+        _on_device(course_len, (Cn,), "int32")
+        _on_device(course_of, (B,), "int32")
         return Cn, Gmax
 
     def plan_window_device(self, courses, course_len, course_of, pose, window_wp: int, stride: int, cursor, plan,
@@ -275,25 +278,27 @@ class BatchSolver:
         courses [C,Gmax,2] float64, course_len [C] and course_of [B] int32, pose [B,3]; cursor [B]
         int32 in/out, plan [B,Mmax,2] float64 and count [B] int32 out, Mmax =
         closed_loop.plan_window_mmax(window_wp, stride)."""
-        import torch
-
         B = pose.shape[0]
         Cn, Gmax = self._courses(courses, course_len, course_of, B)
         Mmax = plan.shape[1]
-        for t, shape, dt in ((pose, (B, 3), torch.float64), (plan, (B, Mmax, 2), torch.float64),
-                             (cursor, (B,), torch.int32), (count, (B,), torch.int32)):
-            assert t.is_cuda and t.dtype == dt and t.is_contiguous() and tuple(t.shape) == shape
+        for t, shape, dt in ((pose, (B, 3), "float64"), (plan, (B, Mmax, 2), "float64"), (cursor, (B,), "int32"),
+                             (count, (B,), "int32")):
+            _on_device(t, shape, dt)
         want = _lib.lib().mpcg_plan_window_mmax(int(window_wp), int(stride))
         assert want < 0 or Mmax == want, f"plan must have Mmax = {want} rows per robot"
-        if stream is None:
-            stream = torch.cuda.current_stream(pose.device)
-        ptr = lambda t: C.c_void_p(t.data_ptr())  # noqa: E731
+        ptr = _ptr
         _lib.check(_lib.lib().mpcg_plan_window_device(
             self._h, B, ptr(courses), ptr(course_len), ptr(course_of), Cn, Gmax, ptr(pose), int(window_wp), int(stride),
-            ptr(cursor), ptr(plan), ptr(count), C.c_void_p(stream.cuda_stream)), "mpcg_plan_window_device")
+            ptr(cursor), ptr(plan), ptr(count), _stream_ptr(stream, pose)), "mpcg_plan_window_device")
 
     ROLLOUT_LOGS = {"pose": 3, "vel": 3, "cmd": 3, "cursor": 0, "start": 0, "count": 0, "status": 0, "iters": 0,
                     "ref_v": 0}
+
+    @classmethod
+    def _log_spec(cls, name, K, B):
+        """A rollout log's shape and dtype name: the 3-wide ones and ref_v are float64, the rest int32."""
+        w = cls.ROLLOUT_LOGS[name]
+        return ((K, B, w) if w else (K, B)), ("float64" if w or name == "ref_v" else "int32")
 
     def rollout_logs(self, K: int, B: int, names=None) -> dict:
         """Log tensors for rollout(K, ..., logs=): pose, vel, cmd [K,B,3] and ref_v [K,B] float64,
@@ -303,9 +308,8 @@ class BatchSolver:
         dev = torch.device("cuda", self.device)
         out = {}
         for n in (names if names is not None else self.ROLLOUT_LOGS):
-            w = self.ROLLOUT_LOGS[n]
-            dt = torch.float64 if w or n == "ref_v" else torch.int32
-            out[n] = torch.zeros((K, B, w) if w else (K, B), dtype=dt, device=dev)
+            shape, dt = self._log_spec(n, K, B)
+            out[n] = torch.zeros(shape, dtype=getattr(torch, dt), device=dev)
         return out
 
     def rollout(self, K: int, courses, course_len, course_of, window_wp: int, stride: int, pose, vel, cursor, ref_v,
@@ -319,27 +323,20 @@ class BatchSolver:
         which robot b stopped, at its goal (within goal_tol) or at its course's end.  logs: tensors
         by name as rollout_logs(K, B) makes them.  No host synchronisation; call it once before
         capturing it in a graph (the handle's buffers grow on first use)."""
-        import torch
-
         B = pose.shape[0]
         Cn, Gmax = self._courses(courses, course_len, course_of, B)
-        for t, shape, dt in ((pose, (B, 3), torch.float64), (vel, (B, 3), torch.float64), (ref_v, (B,), torch.float64),
-                             (cursor, (B,), torch.int32), (done, (B,), torch.int32)):
-            assert t.is_cuda and t.dtype == dt and t.is_contiguous() and tuple(t.shape) == shape
+        for t, shape, dt in ((pose, (B, 3), "float64"), (vel, (B, 3), "float64"), (ref_v, (B,), "float64"),
+                             (cursor, (B,), "int32"), (done, (B,), "int32")):
+            _on_device(t, shape, dt)
         lg = _lib.MpcgRolloutLogs()
         for n, t in (logs or {}).items():
-            w = self.ROLLOUT_LOGS[n]
-            dt = torch.float64 if w or n == "ref_v" else torch.int32
-            assert t.is_cuda and t.dtype == dt and t.is_contiguous()
-            assert tuple(t.shape) == ((K, B, w) if w else (K, B)), n
+            _on_device(t, *self._log_spec(n, K, B))
             setattr(lg, n, t.data_ptr())
-        if stream is None:
-            stream = torch.cuda.current_stream(pose.device)
-        ptr = lambda t: C.c_void_p(t.data_ptr())  # noqa: E731
+        ptr = _ptr
         _lib.check(_lib.lib().mpcg_rollout_device(
             self._h, B, int(K), ptr(courses), ptr(course_len), ptr(course_of), Cn, Gmax, int(window_wp), int(stride),
             float(goal_tol), float(max_speed), float(min_speed), int(bool(delay_mode)), int(bool(integrate)),
-            ptr(pose), ptr(vel), ptr(cursor), ptr(ref_v), ptr(done), C.byref(lg), C.c_void_p(stream.cuda_stream)),
+            ptr(pose), ptr(vel), ptr(cursor), ptr(ref_v), ptr(done), C.byref(lg), _stream_ptr(stream, pose)),
             "mpcg_rollout_device")
 
 

@@ -1,5 +1,5 @@
 // tests/native/wide_plan_check.cpp -- the launch plan of the wavefront solver
-// (mpc_ros_amd/csrc/wide_plan.h: instance choice and workspace layout) on the host; no GPU
+// (mpc_ros_amd/csrc/wide_plan.h: instance choice, workspace layout, tick scratch layout) on the host; no GPU
 // runtime.  Checks the properties below (exit status 1 and a message at the first that fails),
 // then prints the chosen solve instance over the whole input space as JSON, run-length encoded
 // over the horizon: {"model<m>_precision<p>_<default|option>_B<B>": [[N from, N to, name], ...]}
@@ -209,9 +209,44 @@ static int check_layouts() {
     return cases;
 }
 
+// ------------------------------------------------------------------ the tick scratch
+static int check_tick_layouts() {
+    int cases = 0;
+    for (int64_t B : {1, 63, 64, 65, 4097})
+        for (int Mmax : {0, 2, 11, 64})
+            for (int rows : {0, 1}) {
+                const TickLayout L(B, Mmax, rows);
+                char what[64];
+                std::snprintf(what, sizeof what, "tick B %lld Mmax %d rows %d", (long long)B, Mmax, rows);
+                ++cases;
+                // the regions in the stated order, each from an 8-byte boundary, none overlapping the
+                // next; the int32 regions last; the total is the end of the last one
+                const Region* r[] = {&L.state, &L.coeffs, &L.u0, &L.rows, &L.cmd, &L.plan, &L.count, &L.start};
+                CHECK(r[0]->off == 0, "%s", what);
+                for (int i = 0; i < 8; ++i) {
+                    CHECK(r[i]->off % 8 == 0, "%s: region %d at %zu", what, i, r[i]->off);
+                    if (i > 0) CHECK(r[i]->off == r[i - 1]->end(), "%s: region %d", what, i);
+                }
+                CHECK(L.total == L.start.end(), "%s: total", what);
+                // each holds what it is for
+                const size_t b = (size_t)B, roll = Mmax > 0 ? b : 0;
+                CHECK(L.state.bytes == 48 * b && L.coeffs.bytes == 32 * b && L.u0.bytes == 16 * b, "%s: the solve's", what);
+                CHECK(L.rows.bytes == (rows ? 8 * 16 * b : 0), "%s: rows", what);
+                CHECK(L.cmd.bytes == 24 * roll && L.plan.bytes == 16 * (size_t)Mmax * roll, "%s: cmd, plan", what);
+                CHECK(L.count.bytes >= 4 * roll && L.start.bytes >= 4 * roll, "%s: count, start", what);
+                // the plain tick: 12 B doubles; in all what the three buffers it replaces took (12 B,
+                // 16 B and (2 Mmax + 3) B doubles + 2 B int32), but for the two int32 regions'
+                // padding to whole doubles (an odd B)
+                if (!rows && !Mmax) CHECK(L.total == 96 * b, "%s: the plain tick", what);
+                const size_t before = 96 * b + (rows ? 128 * b : 0) + (8 * (2 * (size_t)Mmax + 3) + 8) * roll;
+                CHECK(L.total == before + (B % 2 ? 8 * roll / b : 0), "%s: footprint %zu, was %zu", what, L.total, before);
+            }
+    return cases;
+}
+
 int main() {
     check_instances();
-    const int cases = check_layouts();
+    const int cases = check_layouts() + check_tick_layouts();
     std::fprintf(stderr, "wide_plan_check: %d layouts ok\n", cases);
     return 0;
 }

@@ -340,6 +340,38 @@ def test_tick_with_deceleration_matches_oracle_pipeline(torch_cuda, oracle):  # 
     np.testing.assert_array_equal(c2, c)  # (the same REF_V, the same solve)
 
 
+@pytest.mark.parametrize("M", [11, 65])
+def test_plain_tick_is_the_goal_tick_far_from_every_goal(torch_cuda, M):  # noqa: F811
+    """64 robots of the benchmark generator, plans of 11 waypoints and of 65 (the shortest that
+    takes the HBM-workspace QR): mpcg_track_device equals mpcg_track_device_goal with every goal
+    10 m away in x and y and the handle's REF_V in ref_v -- cmd, traj and status bitwise, ref_v
+    unchanged.  The two run different solver instances (k_solve_wide, k_solve_wide_pp) on one
+    pipeline."""
+    torch = torch_cuda
+    from mpc_ros_amd import params
+    from mpc_ros_amd.solver import BatchSolver
+
+    P = params.PLUGIN_DEFAULTS
+    B, N = 64, int(P["STEPS"])
+    s = BatchSolver(0, P)
+    pose, vel, plan = s.synth_infinity_device(9000, B, M=M)
+    out = []
+    for goal in (False, True):
+        cmd = torch.full((B, 3), 7.0, dtype=torch.float64, device="cuda:0")
+        traj = torch.full((B, 3, N), 7.0, dtype=torch.float64, device="cuda:0")
+        status = torch.full((B,), -7, dtype=torch.int32, device="cuda:0")
+        ref_v = torch.full((B,), float(P["REF_V"]), dtype=torch.float64, device="cuda:0")
+        kw = dict(goal=(pose[:, :2] + 10.0).contiguous(), ref_v=ref_v) if goal else {}
+        s.track_device(pose, vel, plan, cmd, traj=traj, status=status, **kw)
+        torch.cuda.synchronize()
+        assert s.last_kernel.startswith("k_solve_wide_pp<" if goal else "k_solve_wide<"), s.last_kernel
+        out.append((cmd.cpu().numpy(), traj.cpu().numpy(), status.cpu().numpy()))
+        assert (ref_v.cpu().numpy() == P["REF_V"]).all()
+    for name, a, b in zip(("cmd", "traj", "status"), *out):
+        assert a.tobytes() == b.tobytes(), name
+    assert (out[0][0] != 7.0).all() and (out[0][2] != -7).all()  # (written, not the fill values)
+
+
 def test_tick_argument_errors_leave_ref_v_alone(torch_cuda):  # noqa: F811
     """A plan of fewer than 4 waypoints is refused before anything is queued: ref_v (in/out) is
     not rewritten by a call that fails."""

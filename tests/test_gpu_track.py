@@ -227,6 +227,63 @@ def test_two_streams_share_one_handle(torch_cuda):
         np.testing.assert_array_equal(o.cpu().numpy(), r)
 
 
+def test_two_kinds_of_tick_on_two_streams_share_the_scratch(torch_cuda):
+    """One handle: a plain tick of 96 robots on one stream and a K = 2 rollout of the 96-robot
+    scene on another, queued back to back without a host synchronisation (either first).  Both
+    use the handle's one tick scratch, from the same offsets; the second waits for the first
+    one's use, and each equals its solo result bitwise.  (Each runs alone first: the buffers
+    have grown.)"""
+    torch = torch_cuda
+    from mpc_ros_amd import infinity
+    from test_gpu_rollout import Loop
+
+    loop = Loop(torch)
+    s, B, N = loop.s, loop.B, loop.s.N
+    dev = torch.device("cuda:0")
+    sc = infinity.draw_scenarios(np.arange(7000, 7000 + B))
+    px, py, yaw, plan = infinity.scenario_poses(sc)
+    t = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64)).to(dev)  # noqa: E731
+    pose, vel, tplan = t(np.stack([px, py, yaw], 1)), t(np.stack([sc["v"], sc["w_prev"], sc["a_prev"]], 1)), t(plan)
+
+    def outputs():
+        """fresh outputs of both, the rollout's inputs restored; nothing pending on the device"""
+        loop.restore()
+        tick = dict(cmd=torch.full((B, 3), 7.0, dtype=torch.float64, device=dev),
+                    traj=torch.full((B, 3, N), 7.0, dtype=torch.float64, device=dev),
+                    status=torch.full((B,), -7, dtype=torch.int32, device=dev))
+        logs = s.rollout_logs(2, B)
+        torch.cuda.synchronize()
+        return tick, logs
+
+    def plain(tick, stream=None):
+        s.track_device(pose, vel, tplan, tick["cmd"], traj=tick["traj"], status=tick["status"], stream=stream)
+
+    def results(tick, logs):
+        torch.cuda.synchronize()
+        r = {"tick." + k: v.cpu().numpy() for k, v in tick.items()}
+        r.update({"log." + k: v.cpu().numpy() for k, v in logs.items()})
+        r.update({"final." + k: v for k, v in loop.final().items()})
+        return r
+
+    tick, logs = outputs()
+    plain(tick)
+    torch.cuda.synchronize()
+    loop.call(2, logs)
+    solo = results(tick, logs)
+    assert (solo["tick.cmd"] != 7.0).all() and (solo["log.iters"][0] > 0).sum() > 80
+    s1, s2 = torch.cuda.Stream(dev), torch.cuda.Stream(dev)
+    for plain_first in (True, False):
+        tick, logs = outputs()
+        if plain_first:
+            plain(tick, stream=s1)
+        loop.call(2, logs, stream=s2)
+        if not plain_first:
+            plain(tick, stream=s1)
+        both = results(tick, logs)
+        for name in solo:
+            assert both[name].tobytes() == solo[name].tobytes(), (name, plain_first)
+
+
 def test_synthetic_robots_on_device_match_host_generator(torch_cuda):
     """mpcg_synth_infinity_device: the benchmark's robots generated on the GPU from (seed, global
     index) equal infinity.py's host generator (the integer hash bitwise, the trigonometry within

@@ -124,7 +124,8 @@ def test_launch_plan_native_check(tmp_path):
     """tests/native/wide_plan_check.cpp (mpc_ros_amd/csrc/wide_plan.h on the host, no GPU
     runtime): every chosen solve / resume / warm key is an instance the library carries and
     every instance is chosen by some input; the workspace layout's regions are in order, aligned
-    and disjoint for every horizon class, precision, park capacity and batch size.  The solve
+    and disjoint for every horizon class, precision, park capacity and batch size, and so are the
+    regions of a control tick's scratch (TickLayout) over B x Mmax x rows or none.  The solve
     instance it chooses over model x precision x N = 1..128 x default / non-default options x
     B in {1, 4096, 4097} equals the recorded choice of the dispatcher before the plan was a
     header (tests/golden/launch_plan.json), which holds the names the GPU tests pin."""
