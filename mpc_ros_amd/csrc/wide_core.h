@@ -35,7 +35,22 @@
 
 #include "ipm_core.h"
 
+#ifndef MPCG_FUSE
+#define MPCG_FUSE 3
+#endif
+
 namespace mpcg {
+
+// A value the compiler treats as unknown (device: an empty asm on its register): what is
+// computed from it shares no subexpression with the code before it, so an expression written
+// the same way in two sweeps contracts to the same fused multiply-adds in both.
+template <class T>
+MPCG_HD T opaque(T v) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    asm volatile("" : "+v"(v));
+#endif
+    return v;
+}
 
 // LDS layout of one problem (doubles).
 //
@@ -258,6 +273,26 @@ struct WideSolver {
     // accepted (the accepted iterate is bitwise the trial point: both are w + alpha dw)
     T c_sa = 0, c_ca = 0;
     int c_ok = 0;
+    // SPLIT, fused sweeps (MPCG_FUSE: bit 0 the stage data, bit 1 the accepted trial point's
+    // sums; 0 keeps the separate passes -- tests/native/wide_fused_check.cpp compares the two).
+    // FUSE_SQ: the statistics sweep also writes the Newton system's SQD / SQV of its lane's four
+    // variables (precompute_split's mode 0 with delta_w = 0 at the current mu: it holds every
+    // operand), and sq_ok records that the stage table holds them for the iterate in LDS and
+    // the current mu: riccati() then skips the stage-data sweep.  Cleared where mu changes
+    // (k_begin) and by whatever else writes SQD / SQV or replaces the iterate (see sq_drop()).
+    // FUSE_RED: the statistics sweep of an accepted trial point (c_ok) takes the objective,
+    // log-barrier and violation sums (tr_f, tr_lg, tr_theta) the trial sweep reduced at bitwise
+    // the same point instead of evaluating and reducing them again.
+    // fp64 only: in the fp32 split instance the fused statistics sweep compiles to other
+    // contractions (its outputs move in the last bits and 277 of 65,536 iteration counts with
+    // them), and that solver's set of rows in another local minimum moves with rounding -- it
+    // keeps its separate passes.
+    static constexpr bool FUSE_SQ = SPLIT && sizeof(TT) == 8 && (MPCG_FUSE & 1) != 0;
+    static constexpr bool FUSE_RED = SPLIT && sizeof(TT) == 8 && (MPCG_FUSE & 2) != 0;
+    int sq_ok = 0;
+    MPCG_HD void sq_drop() {
+        if constexpr (FUSE_SQ) sq_ok = 0;
+    }
     static constexpr int model = MODEL;
     T lf;  // model 1: wheelbase
 
@@ -600,11 +635,16 @@ struct WideSolver {
     MPCG_HD void stats_split(bool acc, T alpha, T amax_z) {
         const int t = wv.lane();
         accept_all(t, acc, alpha, amax_z);
+        wv.mark(16);
         const bool reuse = acc && c_ok;  // (uniform)
         c_ok = 0;
+        // the trial sweep reduced the objective, log-barrier and violation sums at this point
+        const bool sums_known = FUSE_RED && reuse;
         const int k = t & 31;
         const bool hi = t >= 32, act = k < N, last = k == N - 1;
         const int j0 = hi ? 4 : 0, nr = hi ? 2 : 4;
+        const int sbk = L.ST(k);
+        T sqd[4] = {0, 0, 0, 0}, sqv[4] = {0, 0, 0, 0};
         T f = 0, th = 0, pinf = 0, puns = 0, dinf = 0, mn = (T)INFINITY, mx = -(T)INFINITY, ly = 0, lz = 0,
           lg = 0;
         T Fa[4] = {0, 0, 0, 0}, A[4] = {0, 0, 0, 0};
@@ -696,14 +736,12 @@ struct WideSolver {
                     if (k == 0) st(L.C0() + j, -c);  // initial-state rows of the Newton system
                     const T rsc = rowscale(j, k);
                     const T cs = rsc * c;
-                    th += fabs(cs);
+                    if (!sums_known) th += fabs(cs);
                     pinf = tmax(pinf, (T)fabs(cs));
                     puns = tmax(puns, (T)fabs(c));
                     ly += fabs(yq[q]) * rcp(rsc);
                 }
             }
-            const T e1 = w[4] - (T)P.ref_cte, e2 = w[5] - (T)P.ref_eth, e3 = w[3] - (T)P.ref_v;
-            T fu = (T)P.w_cte * e1 * e1 + (T)P.w_eth * e2 * e2;
             // gradient of the Lagrangian's constraint part, A^T yn (AT_mul) and B^T yn
             T at[4] = {0, 0, 0, 0}, gu[2] = {0, 0};
             if (!last) {
@@ -717,9 +755,13 @@ struct WideSolver {
                     if (model == 1) at[3] += tvk * (yn[2] + yn[5]);
                 }
                 grad_ctrl(k, um, w + 6, up, gu);
-                fu += cost_ctrl(k, w + 6, up);
             }
-            f = hi ? fu : (T)P.w_v * e3 * e3;
+            if (!sums_known) {
+                const T e1 = w[4] - (T)P.ref_cte, e2 = w[5] - (T)P.ref_eth, e3 = w[3] - (T)P.ref_v;
+                T fu = (T)P.w_cte * e1 * e1 + (T)P.w_eth * e2 * e2;
+                if (!last) fu += cost_ctrl(k, w + 6, up);
+                f = hi ? fu : (T)P.w_v * e3 * e3;
+            }
             const T btw = twk * (yn[2] + yn[5]), bta = dt * yn[3];
             // the objective gradient of this half's variables (scaled): g3 / g4, g5, gu
             const T g3 = (T)(2.0 * P.w_v) * (w[3] - (T)P.ref_v);
@@ -740,30 +782,62 @@ struct WideSolver {
                     const T lo = q < 2 ? sl : (q == 2 ? (hi ? wl : sl) : (hi ? al : sl));
                     const T hb = q < 2 ? su : (q == 2 ? (hi ? wu : su) : (hi ? au : su));
                     const T dl = wq - lo, du = hb - wq;
-                    slackprod *= dl * du;
+                    if (!sums_known) slackprod *= dl * du;
                     const T p1 = dl * zl[q], p2 = du * zu[q];
                     mn = tmin(mn, tmin(p1, p2));
                     mx = tmax(mx, tmax(p1, p2));
                     lz += fabs(zl[q]) + fabs(zu[q]);
+                    if constexpr (FUSE_SQ) {
+                        // the Newton system's barrier Hessian diagonal and gradient of this
+                        // variable: precompute_split's expressions, mode 0, delta_w = 0
+                        const T gq = opaque(hi ? (q == 0 ? g4 : (q == 1 ? g5 : gu[q - 2])) : (q == 3 ? g3 : (T)0));
+                        const T hq = hi ? (q < 2 ? hess_state(4 + q) : hess_ctrl(k, q - 2)) : hess_state(q);
+                        sq_terms(hq, gq, wq - lo, hb - wq, zl[q], zu[q], &sqd[q], &sqv[q]);
+                    }
                 }
             }
-            lg = log(slackprod);
+            if (!sums_known) lg = log(slackprod);
+            if constexpr (FUSE_SQ) {
+                // (the last stage's controls: R = r = 0)
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    st(sbk + WideLayout::SQD + j0 + q, sqd[q]);
+                    st(sbk + WideLayout::SQV + j0 + q, sqv[q]);
+                }
+            }
         }
+        if constexpr (FUSE_SQ) sq_ok = 1;
         // (max |z s| = max(max z s, -min z s): one reduction fewer)
-        T v[10] = {f, th, pinf, puns, dinf, mn, mx, ly, lz, lg};
-        const int op[10] = {RSUM, RSUM, RMAX, RMAX, RMAX, RMIN, RMAX, RSUM, RSUM, RSUM};
-        reduce<10, true>(v, op);
-        fval = v[0];
-        theta = v[1];
-        prim_inf = v[2];
-        prim_uns = v[3];
-        dual_inf = v[4];
-        pmin = v[5];
-        pmax = v[6];
+        if (sums_known) {
+            T v[7] = {pinf, puns, dinf, mn, mx, ly, lz};
+            const int op[7] = {RMAX, RMAX, RMAX, RMIN, RMAX, RSUM, RSUM};
+            reduce<7, true>(v, op);
+            fval = tr_f;
+            theta = tr_theta;
+            prim_inf = v[0];
+            prim_uns = v[1];
+            dual_inf = v[2];
+            pmin = v[3];
+            pmax = v[4];
+            l1y = v[5];
+            l1z = v[6];
+            logsum = tr_lg;
+        } else {
+            T v[10] = {f, th, pinf, puns, dinf, mn, mx, ly, lz, lg};
+            const int op[10] = {RSUM, RSUM, RMAX, RMAX, RMAX, RMIN, RMAX, RSUM, RSUM, RSUM};
+            reduce<10, true>(v, op);
+            fval = v[0];
+            theta = v[1];
+            prim_inf = v[2];
+            prim_uns = v[3];
+            dual_inf = v[4];
+            pmin = v[5];
+            pmax = v[6];
+            l1y = v[7];
+            l1z = v[8];
+            logsum = v[9];
+        }
         compl0 = wv.uni_d(tmax(pmax, -pmin));
-        l1y = v[7];
-        l1z = v[8];
-        logsum = v[9];
         wv.mark(0);
     }
 
@@ -1118,6 +1192,14 @@ struct WideSolver {
     }
 
     // ------------------------------------------------------- Riccati backward
+    // The barrier Hessian diagonal (without delta_w) and the barrier gradient of one variable
+    // with slacks dl, du (mode 0): one body for precompute_split and for the statistics sweep
+    // that writes the same entries (FUSE_SQ).  qd > 0, so adding delta_w = 0 changes no bit.
+    MPCG_HD void sq_terms(T hq, T gq, T dl, T du, T zl, T zu, T* qd, T* qv) const {
+        const T rdl = rcp(dl), rdu = rcp(du);
+        *qd = sf * hq + zl * rdl + zu * rdu;
+        *qv = sf * gq - mu * rdl + mu * rdu;
+    }
     // Stage data that does not depend on the cost-to-go, all stages in parallel.
     // Stage data of the Newton system (SPLIT): the lower half-wave takes the barrier
     // Hessian diagonal and gradient of stage k's variables 0..3, the upper of 4..7 (the
@@ -1180,9 +1262,8 @@ struct WideSolver {
                 const T lo = q < 2 ? sl : (q == 2 ? (hi ? wl : sl) : (hi ? al : sl));
                 const T hb = q < 2 ? su : (q == 2 ? (hi ? wu : su) : (hi ? au : su));
                 if (mode == 0) {
-                    const T rdl = rcp(w[q] - lo), rdu = rcp(hb - w[q]);
-                    qd = sf * hq + zl[q] * rdl + zu[q] * rdu + delta_w;
-                    qv = sf * gq - mu * rdl + mu * rdu;
+                    sq_terms(hq, gq, w[q] - lo, hb - w[q], zl[q], zu[q], &qd, &qv);
+                    qd += delta_w;
                 } else {
                     qd = 1;
                     qv = sf * gq - zl[q] + zu[q];
@@ -1317,7 +1398,14 @@ struct WideSolver {
     MPCG_HD bool riccati(int mode, T delta_w) {
         const int t = wv.lane();  // (recomputed per phase: nothing lane-dependent is hoisted)
         wv.sync();
-        precompute(mode, delta_w);
+        // (FUSE_SQ: the statistics sweep of this iterate wrote SQD / SQV for this mu, delta_w = 0)
+        const bool sq_have = FUSE_SQ && wv.uni(mode == 0 && delta_w == (T)0 && sq_ok != 0);
+        if (!sq_have) {
+            precompute(mode, delta_w);
+            // mode 1 and an inertia-correction retry (delta_w > 0) leave other values behind
+            if constexpr (FUSE_SQ) sq_ok = wv.uni(mode == 0 && delta_w == (T)0);
+        }
+        if constexpr (SPLIT) wv.mark(sq_have ? 14 : 15);  // (the stage-data pass skipped / run)
         typedef WideLayout W_;
         const int i = t >> 3, j = t & 7;
         const int si = aslot(i), sj = aslot(j);
@@ -2027,6 +2115,10 @@ struct WideSolver {
         f = v[0];
         thv = v[1];
         lg = v[2];
+        if constexpr (FUSE_RED) {
+            tr_f = f;
+            tr_lg = lg;
+        }
         const bool anybad = wv.any(bad != 0);
         wv.mark(6);
         *phi = sf * f - mu * lg;
@@ -3525,6 +3617,7 @@ struct WideSolver {
     bool st_acc, sv_ok, tr_ok;
     int sv_mode;
     T st_alpha, st_z, sv_delta, tr_alpha, tr_test, tr_phi, tr_theta, pd_val;
+    T tr_f = 0, tr_lg = 0;  // (SPLIT) the trial point's reduced objective and log-barrier sums
     bool tr_acc;  // the trial point passed CheckAcceptabilityOfTrialPoint(tr_test)
     Fwd sv_F;
     // line-search state (BacktrackingLineSearch)
@@ -3570,6 +3663,7 @@ struct WideSolver {
         mu = wv.uni_d(mu0);
         tau = wv.uni_d(tmax((T)0.99, (T)1 - mu0));
         status = 0;
+        sq_drop();  // (init: the least-squares solve, mode 1; init_warm: a statistics sweep first)
         theta_max() = -1;
         theta_min = -1;
         dw_last = 0;
@@ -3764,6 +3858,7 @@ struct WideSolver {
             if (!changed && tf) return IPM_TINY_STEP;
             mu = mnew;
             tau = wv.uni_d(tmax((T)0.99, (T)1 - mu));
+            if (changed) sq_drop();  // (the stage table's SQD / SQV hold for the old mu)
             if (!changed) {
                 done = true;
             } else {
@@ -3966,6 +4061,7 @@ struct WideSolver {
         xcopy(false, WideLayout::XP, 0, 36);
         wd_short = 0;
         c_ok = 0;
+        sq_drop();  // (the iterate is replaced; its statistics sweep writes the table again)
         return do_stats(false, (T)0, (T)0, K_WD_STATS);
     }
     MPCG_HD int k_wd_stats() {
@@ -4001,6 +4097,10 @@ struct WideSolver {
         xcopy(true, WideLayout::XP, 48, 24);  // (RESTO: p, n, z_p, z_n)
         accept_all(wv.lane(), true, soft_a(), soft_a(), false);
         c_ok = 0;
+        // the iterate moved behind the stage table.  (No Newton system is solved before the next
+        // statistics sweep: an accepted soft step goes on to one, a rejected one -- rec_in of the
+        // kept iterate in k_soft_pd1 -- ends the line search in ls_fail.)
+        sq_drop();
         return set_op(OP_PDERR, K_SOFT_PD1);
     }
     MPCG_HD int k_soft_pd1() {
@@ -4063,7 +4163,8 @@ struct WideSolver {
             // almost feasible: the last acceptable iterate, if any, is the result
             if (wv.uni(theta <= (T)1e-2 * (T)P.tol)) {
                 if (have_acc) {
-                    rec_in<0, 8>(L.SP_ACC());
+                    rec_in<0, 8>(L.SP_ACC());  // (the solve ends here: the stage table is not read again)
+                    sq_drop();
                     return IPM_ACCEPTABLE;
                 }
                 return IPM_RESTORATION_FAILURE;
@@ -4109,6 +4210,7 @@ struct WideSolver {
         iter = wv.uni(o.iter);
         n_fover += wv.uni(o.fover);
         c_ok = 0;
+        sq_drop();  // (a new iterate comes back; its statistics sweep writes the table again)
         const int s = wv.uni(o.status);
         if (s) return s;
         clamp_all();
@@ -4449,6 +4551,7 @@ struct WideSolver {
         nf_peak = wv.uni((int)src[26]);
         status = NEED_RESTO;
         c_ok = 0;
+        sq_drop();  // (not parked: the restoration phase this solver continues with replaces the iterate)
         acc_pending = false;
         cur_acceptable = false;
     }

@@ -20,9 +20,11 @@
 
 namespace mpcg {
 constexpr int NPH = 18;
-// 9..13: sub-phase stamps of diagnostic variants (variants/stamps)
+// stats: the statistics sweep after the accept pass (accept); ric-pre: the Riccati sweep's setup
+// after the stage-data pass (sq-run; sq-skip: the pass skipped, the table written by the
+// statistics sweep); 9..13: the continuations between sweeps
 const char* kPhase[NPH] = {"stats", "ric-pre", "ric-sweep", "fwd-seq", "fwd-adj", "fwd-par", "trial", "ls-rest", "begin-rest",
-                           "pre-trial", "accept-chk", "newton-in", "setref", "step-out", "pre-filter", "filter-add", "pre-lsfin", "pre-kbt"};
+                           "pre-trial", "accept-chk", "newton-in", "setref", "step-out", "sq-skip", "sq-run", "accept", "pre-kbt"};
 
 struct ProfWave : DevWaveBase {
     unsigned long long* acc;
