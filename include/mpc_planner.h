@@ -54,6 +54,11 @@ class MPC {
     int last_iters() const { return _last_iters; }
     double last_obj() const { return _last_obj; }
     int steps() const { return _mpc_steps; }
+    // The full solution of the last Solve (include/mpcg.h mpcg_solve_sol): x | zl | zu | lambda of
+    // the unscaled NLP, mpcg_solution_elems(steps()) doubles.  Off by default -- a default Solve
+    // copies nothing more; empty until a Solve has run with it on.
+    void keep_solution(bool on) { _keep_solution = on; }
+    const vector<double>& solution() const { return _solution; }
     // GPU the solver runs on (default 0); call before the first Solve.
     void set_device(int device) { _device = device; }
 
@@ -71,6 +76,8 @@ class MPC {
     mpcg_handle* _handle;
     int _last_status, _last_iters;
     double _last_obj;
+    bool _keep_solution = false;
+    vector<double> _solution;
 };
 
 #endif /* MPCG_MPC_PLANNER_H */

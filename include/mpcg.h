@@ -459,6 +459,60 @@ int mpcg_rollout_device(mpcg_handle* h, int64_t B, int32_t K, const double* d_co
                         double* d_pose, double* d_vel, int32_t* d_cursor, double* d_ref_v, int32_t* d_done,
                         const mpcg_rollout_logs* logs, void* stream);
 
+/* ---- The full solution and its certificate ----
+ * What CppAD::ipopt::solve_result carries beyond the first control: the primal point and every
+ * multiplier of the ORIGINAL, unscaled NLP, in the reference's vars order (mpc_planner.cpp:252-259)
+ * and FG_eval's row order (fg[1 + i]).  One problem's record, mpcg_solution_elems(N) =
+ * 3 (8N - 2) + 6N doubles:
+ *   x      [8N-2]  x(N) | y(N) | theta(N) | v(N) | cte(N) | etheta(N) | omega(N-1) | a(N-1)
+ *   zl     [8N-2]  lower-bound multipliers (>= 0), same order
+ *   zu     [8N-2]  upper-bound multipliers (>= 0), same order
+ *   lambda [6N]    constraint multipliers, row s N + k (s: x y theta v cte etheta; k = 0 the
+ *                  initial-state row, k >= 1 the dynamics defect of step k - 1)
+ * Ipopt's / CppAD's convention: the Lagrangian is sigma f + sum lambda_i g_i, stationarity reads
+ * grad f + J^T lambda - zl + zu = 0.  The solver's objective and row scaling is undone (Ipopt's
+ * finalize_solution).  x is the point u0 and traj publish (honor_original_bounds applied):
+ * x[0..N), x[N..2N), x[2N..3N) equal traj and x[6N], x[7N-1] equal u0 bit for bit.
+ * solve_result.g is not in the record: at a returned point it is the constraint bounds (state[s]
+ * for row s N, 0 elsewhere) to within the violation the certificate's column 1 reports.
+ * Every ending writes the record: a status other than 1 or 4 the iterate the solve ended with
+ * (what Ipopt hands to finalize_solution), an invalid parameter row (status 13) zeros.  Row p of
+ * sol is problem p's, whatever the solve order. */
+int64_t mpcg_solution_elems(int32_t N);
+/* byte offsets of the four parts within one problem's record */
+#define MPCG_SOL_X_OFFSET(N) ((size_t)0)
+#define MPCG_SOL_ZL_OFFSET(N) ((size_t)(8 * (N) - 2) * sizeof(double))
+#define MPCG_SOL_ZU_OFFSET(N) ((size_t)2 * (8 * (N) - 2) * sizeof(double))
+#define MPCG_SOL_LAMBDA_OFFSET(N) ((size_t)3 * (8 * (N) - 2) * sizeof(double))
+/* mpcg_solve_ex / mpcg_solve_device_ex with the records sol [B][mpcg_solution_elems(N)] (required)
+ * and a parameter row per problem, pparams [B][16] (NULL: the handle's parameters; otherwise as
+ * mpcg_solve_pp / mpcg_solve_device_pp).  The iterates, and with them u0, traj, status, iters and
+ * obj, are bitwise those of the call without sol.  The device call is queued on `stream` like its
+ * twin (no allocation after mpcg_reserve; capturable).  Refused (-1) before anything is launched:
+ * a NULL sol; precision 1 with no_restoration 1 (the fp32 phase alone has no fp64 ending to
+ * report -- with no_restoration 0 the record is the fp64 phase's); precision 1 with rows.
+ * mpcg_multi_* is unchanged: the multi-GPU gather does not carry the record. */
+int mpcg_solve_sol(mpcg_handle* h, int64_t B, const double* state, const double* coeffs, const double* pparams,
+                   double* u0, double* traj, int32_t* status, double* obj, int32_t* iters, int32_t* diag, double* sol);
+int mpcg_solve_device_sol(mpcg_handle* h, int64_t B, const double* d_state, const double* d_coeffs,
+                          const double* d_pparams, double* d_u0, double* d_traj, int32_t* d_status, double* d_obj,
+                          int32_t* d_iters, int32_t* d_diag, double* d_sol, void* stream);
+/* The KKT certificate of B records, from the NLP alone (the reference's FG_eval and MPC::Solve's
+ * original, unrelaxed bounds; no solver code, no scaling): cert [B][4], all unscaled,
+ *   0  || grad f + J^T lambda - zl + zu ||_inf
+ *   1  max(|| g(x) - g_bound ||_inf, the largest bound violation of x)
+ *   2  max over the variables of max(|(x - xl) zl|, |(xu - x) zu|)
+ *   3  f(x)
+ * pparams: a parameter row per problem or NULL (then *p / the handle's parameters); a problem
+ * whose row is outside mpcg_pparams_check's domains gets NaN in all four columns, nothing traps.
+ * mpcg_kkt: host arrays, no GPU and no handle (the code the kernel runs per stage, in a loop).
+ * mpcg_kkt_device: device arrays, one problem per wavefront, queued on `stream`; no allocation,
+ * capturable.  Host and device agree to rounding (sin / cos and the order of the objective's sum). */
+int mpcg_kkt(const mpcg_params* p, int64_t B, const double* state, const double* coeffs, const double* pparams,
+             const double* sol, double* cert);
+int mpcg_kkt_device(mpcg_handle* h, int64_t B, const double* d_state, const double* d_coeffs, const double* d_pparams,
+                    const double* d_sol, double* d_cert, void* stream);
+
 /* The benchmark's synthetic robots (the "infinity set", mpc_ros_amd/infinity.py) generated on
  * the device: robot start + i of the set (i < B) is a pure function of (seed, start + i) --
  * a pose near a lemniscate course, its speed and previous controls, and a plan of M waypoints

@@ -91,6 +91,13 @@ SIGNATURES = {
     "mpcg_solve_pp": ([C.c_void_p, C.c_int64, _dp, _dp, _dp, _dp, _dp, _ip, _dp, _ip, _ip], C.c_int),
     "mpcg_solve_device_pp": ([C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                               C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p], C.c_int),
+    "mpcg_solution_elems": ([C.c_int32], C.c_int64),
+    "mpcg_solve_sol": ([C.c_void_p, C.c_int64, _dp, _dp, _dp, _dp, _dp, _ip, _dp, _ip, _ip, _dp], C.c_int),
+    "mpcg_solve_device_sol": ([C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                               C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p], C.c_int),
+    "mpcg_kkt": ([_PP, C.c_int64, _dp, _dp, _dp, _dp, _dp], C.c_int),
+    "mpcg_kkt_device": ([C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                         C.c_void_p], C.c_int),
     "mpcg_decelerate": ([C.c_double] * 6, C.c_double),
     "mpcg_track_device_goal": ([C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                 C.c_void_p, C.c_double, C.c_double, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,

@@ -38,7 +38,7 @@ MPC::MPC(const MPC& o)
       _y_start(o._y_start), _theta_start(o._theta_start), _v_start(o._v_start), _cte_start(o._cte_start),
       _etheta_start(o._etheta_start), _angvel_start(o._angvel_start), _a_start(o._a_start), _params(o._params),
       _device(o._device), _handle(nullptr), _last_status(o._last_status), _last_iters(o._last_iters),
-      _last_obj(o._last_obj) {}
+      _last_obj(o._last_obj), _keep_solution(o._keep_solution), _solution(o._solution) {}
 
 MPC& MPC::operator=(const MPC& o) {
     if (this == &o) return *this;
@@ -63,6 +63,8 @@ MPC& MPC::operator=(const MPC& o) {
     _last_status = o._last_status;
     _last_iters = o._last_iters;
     _last_obj = o._last_obj;
+    _keep_solution = o._keep_solution;
+    _solution = o._solution;
     return *this;  // keeps its own GPU handle
 }
 
@@ -125,7 +127,14 @@ vector<double> MPC::SolveRaw(const double* state, const double* coeffs) {
     vector<double> traj(3 * (size_t)N);
     double u0[2] = {0, 0}, obj = 0;
     int32_t status = 0, iters = 0;
-    int rc = mpcg_solve(_handle, 1, state, coeffs, u0, traj.data(), &status, &obj, &iters);
+    int rc;
+    if (_keep_solution) {
+        _solution.assign((size_t)mpcg_solution_elems(N), 0.0);
+        rc = mpcg_solve_sol(_handle, 1, state, coeffs, nullptr, u0, traj.data(), &status, &obj, &iters, nullptr,
+                            _solution.data());
+    } else {
+        rc = mpcg_solve(_handle, 1, state, coeffs, u0, traj.data(), &status, &obj, &iters);
+    }
     if (rc) {
         std::fprintf(stderr, "[MPC] solve failed: %s\n", mpcg_last_error());
         _last_status = 13;

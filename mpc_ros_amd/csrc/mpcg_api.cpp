@@ -12,6 +12,7 @@
 
 #include "mpcg.h"
 #include "mpcg_internal.h"
+#include "mpcg_kkt.h"
 #include "mpcg_pp.h"
 #include "mpcg_window.h"
 
@@ -448,7 +449,7 @@ static int lds_refusal(const mpcg_handle* h) {
 // the refusals, grown the solver's scratch (ensure_solve) and ordered s (with_scratch).
 static int queue_solve(mpcg_handle* h, int64_t B, const double* d_state, const double* d_coeffs,
                        const double* d_pparams, double* d_u0, double* d_traj, int32_t* d_status, double* d_obj,
-                       int32_t* d_iters, int32_t* d_diag, hipStream_t s) {
+                       int32_t* d_iters, int32_t* d_diag, hipStream_t s, double* d_sol = nullptr) {
     // batches larger than the resident wavefronts (8 per CU) are solved in
     // expected-longest-first order (launch_wide_order)
     int32_t* order = nullptr;
@@ -464,21 +465,29 @@ static int queue_solve(mpcg_handle* h, int64_t B, const double* d_state, const d
     ws.ev_join2 = h->ev_join2;
     hipError_t e = mpcg::launch_wide_solve(handle_ipm(h), B, d_state, d_coeffs, d_u0, d_traj, d_status, d_obj, d_iters,
                                            d_diag, order, h->d_spill.p, h->d_spill.bytes, s, ws, &h->last_kernel,
-                                           d_pparams);
+                                           d_pparams, d_sol);
     if (e != hipSuccess) return hip_fail(e, "wide solve launch");
     h->last_ordered = order != nullptr;
     return 0;
 }
 
-// the device solve; d_pparams: a parameter row per problem (mpcg_solve_device_pp) or null
+static const char kNoFp32Sol[] =
+    "precision 1 with no_restoration 1 (the fp32 phase alone) has no fp64 ending to report: no solution record";
+
+// the device solve; d_pparams: a parameter row per problem (mpcg_solve_device_pp) or null;
+// want_sol (mpcg_solve_device_sol): the solution records into d_sol
 static int solve_device(mpcg_handle* h, int64_t B, const double* d_state, const double* d_coeffs,
                         const double* d_pparams, double* d_u0, double* d_traj, int32_t* d_status, double* d_obj,
-                        int32_t* d_iters, int32_t* d_diag, void* stream) {
+                        int32_t* d_iters, int32_t* d_diag, void* stream, double* d_sol = nullptr,
+                        bool want_sol = false) {
     int rc = batch_check(h, B);
-    if (rc || B == 0) return rc;
+    if (rc) return rc;
+    if (want_sol && !d_sol) return fail(-1, "sol is required");
+    if (B == 0) return 0;
     if (!d_state || !d_coeffs || !d_u0) return fail(-1, "state, coeffs and u0 are required");
     rc = params_refusal(h, d_pparams != nullptr);
     if (rc) return rc;
+    if (want_sol && h->params.precision == 1 && h->params.no_restoration == 1) return fail(-1, kNoFp32Sol);
     hipError_t e = hipSetDevice(h->device);
     if (e != hipSuccess) return hip_fail(e, "hipSetDevice");
     hipStream_t s = (hipStream_t)stream;  // NULL = the null stream, as in HIP
@@ -486,7 +495,8 @@ static int solve_device(mpcg_handle* h, int64_t B, const double* d_state, const 
     if (rc == 0) rc = ensure_solve(h, B);
     if (rc) return rc;
     return with_scratch(h, s, [&] {
-        return queue_solve(h, B, d_state, d_coeffs, d_pparams, d_u0, d_traj, d_status, d_obj, d_iters, d_diag, s);
+        return queue_solve(h, B, d_state, d_coeffs, d_pparams, d_u0, d_traj, d_status, d_obj, d_iters, d_diag, s,
+                           d_sol);
     });
 }
 
@@ -503,6 +513,15 @@ int mpcg_solve_device_pp(mpcg_handle* h, int64_t B, const double* d_state, const
     return solve_device(h, B, d_state, d_coeffs, d_pparams, d_u0, d_traj, d_status, d_obj, d_iters, d_diag, stream);
 }
 
+int mpcg_solve_device_sol(mpcg_handle* h, int64_t B, const double* d_state, const double* d_coeffs,
+                          const double* d_pparams, double* d_u0, double* d_traj, int32_t* d_status, double* d_obj,
+                          int32_t* d_iters, int32_t* d_diag, double* d_sol, void* stream) {
+    return solve_device(h, B, d_state, d_coeffs, d_pparams, d_u0, d_traj, d_status, d_obj, d_iters, d_diag, stream,
+                        d_sol, true);
+}
+
+int64_t mpcg_solution_elems(int32_t N) { return N >= 2 ? mpcg::solution_elems(N) : 0; }
+
 int mpcg_solve(mpcg_handle* h, int64_t B, const double* state, const double* coeffs, double* u0, double* traj,
                int32_t* status, double* obj, int32_t* iters) {
     return mpcg_solve_ex(h, B, state, coeffs, u0, traj, status, obj, iters, nullptr);
@@ -510,12 +529,16 @@ int mpcg_solve(mpcg_handle* h, int64_t B, const double* state, const double* coe
 
 // the host solve; pparams: a parameter row per problem (mpcg_solve_pp) or null
 static int solve_host(mpcg_handle* h, int64_t B, const double* state, const double* coeffs, const double* pparams,
-                      double* u0, double* traj, int32_t* status, double* obj, int32_t* iters, int32_t* diag) {
+                      double* u0, double* traj, int32_t* status, double* obj, int32_t* iters, int32_t* diag,
+                      double* sol = nullptr, bool want_sol = false) {
     int rc = batch_check(h, B);
-    if (rc || B == 0) return rc;
+    if (rc) return rc;
+    if (want_sol && !sol) return fail(-1, "sol is required");
+    if (B == 0) return 0;
     if (!state || !coeffs || !u0) return fail(-1, "state, coeffs and u0 are required");
     rc = mpcg_params_check(&h->params);
     if (rc) return rc;
+    if (want_sol && h->params.precision == 1 && h->params.no_restoration == 1) return fail(-1, kNoFp32Sol);
     if (pparams) {
         if (h->params.precision != 0) return fail(-1, kNoFp32Rows);
         rc = mpcg_pparams_check(pparams, B, h->params.model, nullptr);
@@ -523,8 +546,10 @@ static int solve_host(mpcg_handle* h, int64_t B, const double* state, const doub
     }
     const int N = h->params.steps;
     // io block: state 6 | coeffs 4 | u0 2 | traj 3N | obj 1 | status+iters (2 int32 = 1 double) |
-    // diag (4 int32 = 2 doubles) | the parameter rows 16 (mpcg_solve_pp)
-    const size_t per = (size_t)(6 + 4 + 2 + 3 * N + 1 + 1 + 2) + (pparams ? MPCG_PP_FIELDS : 0);
+    // diag (4 int32 = 2 doubles) | the parameter rows 16 (mpcg_solve_pp) | the solution records
+    // (mpcg_solve_sol)
+    const size_t nsol = want_sol ? (size_t)mpcg::solution_elems(N) : 0;
+    const size_t per = (size_t)(6 + 4 + 2 + 3 * N + 1 + 1 + 2) + (pparams ? MPCG_PP_FIELDS : 0) + nsol;
     const size_t need = per * sizeof(double) * (size_t)B;
     hipError_t e = hipSetDevice(h->device);
     if (e != hipSuccess) return hip_fail(e, "hipSetDevice");
@@ -539,12 +564,14 @@ static int solve_host(mpcg_handle* h, int64_t B, const double* state, const doub
     int32_t* dit = dst + B;
     int32_t* ddg = dit + B;
     double* dpp = (double*)(ddg + 4 * B);
+    double* dsol = dpp + (pparams ? (size_t)MPCG_PP_FIELDS * B : 0);
     e = hipMemcpyAsync(ds, state, sizeof(double) * 6 * B, hipMemcpyHostToDevice, h->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(dc, coeffs, sizeof(double) * 4 * B, hipMemcpyHostToDevice, h->stream);
     if (e == hipSuccess && pparams)
         e = hipMemcpyAsync(dpp, pparams, sizeof(double) * MPCG_PP_FIELDS * B, hipMemcpyHostToDevice, h->stream);
     if (e != hipSuccess) return hip_fail(e, "hipMemcpy H2D");
-    rc = solve_device(h, B, ds, dc, pparams ? dpp : nullptr, du, dt, dst, dob, dit, diag ? ddg : nullptr, h->stream);
+    rc = solve_device(h, B, ds, dc, pparams ? dpp : nullptr, du, dt, dst, dob, dit, diag ? ddg : nullptr, h->stream,
+                      want_sol ? dsol : nullptr, want_sol);
     if (rc) return rc;
     e = hipMemcpyAsync(u0, du, sizeof(double) * 2 * B, hipMemcpyDeviceToHost, h->stream);
     if (e == hipSuccess && traj)
@@ -556,9 +583,57 @@ static int solve_host(mpcg_handle* h, int64_t B, const double* state, const doub
         e = hipMemcpyAsync(iters, dit, sizeof(int32_t) * B, hipMemcpyDeviceToHost, h->stream);
     if (e == hipSuccess && diag)
         e = hipMemcpyAsync(diag, ddg, sizeof(int32_t) * 4 * B, hipMemcpyDeviceToHost, h->stream);
+    if (e == hipSuccess && want_sol)
+        e = hipMemcpyAsync(sol, dsol, sizeof(double) * nsol * B, hipMemcpyDeviceToHost, h->stream);
     if (e != hipSuccess) return hip_fail(e, "hipMemcpy D2H");
     e = hipStreamSynchronize(h->stream);
     if (e != hipSuccess) return hip_fail(e, "hipStreamSynchronize");
+    return 0;
+}
+
+int mpcg_solve_sol(mpcg_handle* h, int64_t B, const double* state, const double* coeffs, const double* pparams,
+                   double* u0, double* traj, int32_t* status, double* obj, int32_t* iters, int32_t* diag, double* sol) {
+    return solve_host(h, B, state, coeffs, pparams, u0, traj, status, obj, iters, diag, sol, true);
+}
+
+// ---- the KKT certificate (mpcg_kkt.h) ----
+int mpcg_kkt(const mpcg_params* p, int64_t B, const double* state, const double* coeffs, const double* pparams,
+             const double* sol, double* cert) {
+    if (!p) return fail(-1, "null params");
+    if (B < 0) return fail(-1, "negative batch");
+    if (B == 0) return 0;
+    if (!state || !coeffs || !sol || !cert) return fail(-1, "state, coeffs, sol and cert are required");
+    int rc = mpcg_params_check(p);
+    if (rc) return rc;
+    const mpcg::IpmParams P = to_ipm(*p);
+    const mpcg::PPRow row = mpcg::pp_row_pack(P);
+    const int64_t ne = mpcg::solution_elems(P.N);
+    for (int64_t b = 0; b < B; ++b) {
+        const mpcg::KktCert c = mpcg::kkt_problem(pparams ? pparams + b * MPCG_PP_FIELDS : row.f, P.model, P.N,
+                                                  state + b * 6, coeffs + b * 4, sol + b * ne);
+        cert[b * 4 + 0] = c.stat;
+        cert[b * 4 + 1] = c.prim;
+        cert[b * 4 + 2] = c.comp;
+        cert[b * 4 + 3] = c.f;
+    }
+    return 0;
+}
+
+int mpcg_kkt_device(mpcg_handle* h, int64_t B, const double* d_state, const double* d_coeffs, const double* d_pparams,
+                    const double* d_sol, double* d_cert, void* stream) {
+    int rc = batch_check(h, B);
+    if (rc || B == 0) return rc;
+    if (!d_state || !d_coeffs || !d_sol || !d_cert) return fail(-1, "state, coeffs, sol and cert are required");
+    rc = mpcg_params_check(&h->params);
+    if (rc) return rc;
+    if (h->params.steps > 128) return fail(-1, "STEPS must be <= 128");
+    hipError_t e = hipSetDevice(h->device);
+    if (e != hipSuccess) return hip_fail(e, "hipSetDevice");
+    const mpcg::IpmParams P = handle_ipm(h);
+    // (no handle scratch is touched: nothing to order against the handle's other streams)
+    e = mpcg::launch_kkt_certify(B, P.N, P.model, mpcg::pp_row_pack(P), d_pparams, d_state, d_coeffs, d_sol, d_cert,
+                                 (hipStream_t)stream);
+    if (e != hipSuccess) return hip_fail(e, "kkt certificate launch");
     return 0;
 }
 

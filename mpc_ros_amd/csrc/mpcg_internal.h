@@ -34,9 +34,16 @@ hipError_t launch_wide_solve(const IpmParams& P, int64_t B, const double* state,
                              double* traj, int32_t* status, double* obj, int32_t* iters, int32_t* diag,
                              const int32_t* order, void* spill, size_t spill_bytes, hipStream_t stream,
                              const WideStreams& ws = WideStreams(), const char** kernel_name = nullptr,
-                             const double* pparams = nullptr);
+                             const double* pparams = nullptr, double* sol = nullptr);
 // (pparams: a parameter row per problem, [B][16] doubles in include/mpcg.h's MPCG_PP_* order,
 // on the device -- the k_solve_wide_pp / k_resume_wide_pp instances; fp64 only)
+// (sol: the solution records [B][solution_elems(N)] on the device, written by every ending's
+// write_out -- WideSolver::solution_out -- or null)
+// The certificate (mpcg_kkt.hip): cert [B][4] from the NLP alone at the records sol; `row` the
+// handle's per-problem fields, rows [B][16] (or null) a row per problem.
+struct PPRow;
+hipError_t launch_kkt_certify(int64_t B, int N, int model, const PPRow& row, const double* rows, const double* state,
+                              const double* coeffs, const double* sol, double* cert, hipStream_t stream);
 // Solve order (expected-longest first): device buffer bytes for B problems, and the
 // launch that writes the workgroup -> problem map into `buf` (returned in *order).
 size_t wide_sched_bytes(int64_t B);

@@ -186,6 +186,7 @@ struct WideProblem {
     double* obj;
     int32_t *iters, *diag;
     int64_t n_prob;
+    double* sol = nullptr;  // the solution records [n_prob][solution_elems(N)], or null
 };
 // One batch launch (with its resume workers, drain and overflow launches): the instance inst for
 // parameters P, on B problems in the given order, on the workspace `lay` at base.  handoff: the
@@ -258,7 +259,8 @@ static hipError_t launch_phase(const WideProblem& pb, const PhaseLaunch& L, bool
                .started = cnt + PhaseLayout::STARTED, .ovf_count = cnt + PhaseLayout::OVF_COUNT,
                .ovf_taken = cnt + PhaseLayout::OVF_TAKEN, .ovf_idx = (int64_t*)(L.base + W.ovf.off),
                .nxcc = (int32_t)W.nxcc, .phase = 0, .ent0 = 0, .ovf_mark = 2, .handoff = L.handoff,
-               .handoff_stride = L.handoff ? L.handoff_stride : 0};
+               .handoff_stride = L.handoff ? L.handoff_stride : 0, .sol = pb.sol,
+               .sol_stride = solution_elems(P.N)};
     // (the per-problem kernels take the rows as a second argument, after WideArgs)
     const double* rows = L.pparams;
     void* args[] = {(void*)&a, (void*)&rows};
@@ -326,12 +328,13 @@ static hipError_t launch_phase(const WideProblem& pb, const PhaseLaunch& L, bool
 hipError_t launch_wide_solve(const IpmParams& P, int64_t B, const double* state, const double* coeffs, double* u0,
                              double* traj, int32_t* status, double* obj, int32_t* iters, int32_t* diag,
                              const int32_t* order, void* spill, size_t spill_bytes, hipStream_t stream,
-                             const WideStreams& ws, const char** kernel_name, const double* pparams) {
+                             const WideStreams& ws, const char** kernel_name, const double* pparams,
+                             double* sol) {
     if (B <= 0) return hipSuccess;
     if (!spill) return hipErrorInvalidValue;
     const SolveLayout W = solve_layout(P, B);
     if (W.total > spill_bytes) return hipErrorInvalidValue;
-    const WideProblem pb{state, coeffs, u0, traj, status, obj, iters, diag, B};
+    const WideProblem pb{state, coeffs, u0, traj, status, obj, iters, diag, B, sol};
     // (per-problem rows: the same workspace -- the per-problem instance has its plain twin's LDS
     // size and register allocation, so the slot budget is the plain instance's)
     PhaseLaunch L{.P = P, .inst = pparams ? wide_pp_kernel(P, B) : wide_kernel(P, B), .B = B, .order = order,

@@ -65,6 +65,10 @@ struct WideArgs {
     // kernel, read by k_warm_wide and its resume workers; handoff_stride floats per problem
     float* handoff;
     int64_t handoff_stride;
+    // the solution record (WideSolver::solution_out: x, z_L, z_U, lambda of the unscaled NLP), row p
+    // of sol_stride doubles, or null (every caller but mpcg_solve_device_sol)
+    double* sol;
+    int64_t sol_stride;
 };
 // Always-on range checks of the indices a kernel reads from device memory (the solve order, the
 // park area's problem indices, the overflow list, a parked entry's counts) or derives from the
@@ -189,6 +193,8 @@ __device__ __forceinline__ void pp_invalid_out(const WideArgs& a, int64_t p) {
     if (a.diag && t < 4) a.diag[p * 4 + t] = 0;
     if (a.traj)
         for (int k = t; k < 3 * a.P.N; k += 64) a.traj[p * 3 * a.P.N + k] = 0.0;
+    if (a.sol)
+        for (int64_t e = t; e < a.sol_stride; e += 64) a.sol[p * a.sol_stride + e] = 0.0;
 }
 
 // WPE: wavefronts per SIMD the register allocation is for -- 2 (256 VGPRs), 1 (512) for the
@@ -341,6 +347,7 @@ __device__ __forceinline__ void write_out(const WideArgs& a, Solver& S, int64_t 
             tr[2 * N + k] = (double)S.x_state(2, k);
         }
     }
+    if (a.sol) S.solution_out(a.sol + p * a.sol_stride);
 }
 
 // The parked problems: the restoration phase (WideSolver<..., RESTO> out of line) and the

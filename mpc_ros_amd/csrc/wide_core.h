@@ -164,6 +164,9 @@ struct WideLayout {
     MPCG_HD static int handoff(int N_) { return HANDOFF_HEAD + 30 * N_; }
 };
 
+// doubles of one problem's solution record (WideSolver::solution_out): x, z_L, z_U (8N - 2 each), lambda (6N)
+MPCG_HD int64_t solution_elems(int N) { return 3 * (int64_t)(8 * N - 2) + 6 * (int64_t)N; }
+
 // The original problem's values the restoration phase needs (passed by value into its
 // out-of-line function) and its result.
 template <class T>
@@ -4610,6 +4613,34 @@ struct WideSolver {
             }
         }
         return rsum(f);
+    }
+    // The solution record of the ORIGINAL, unscaled NLP (include/mpcg.h MPCG_SOL_*), 3 (8N - 2) + 6N
+    // doubles in the reference's vars / FG_eval row order: x | z_L | z_U | lambda, with the
+    // Lagrangian sigma f + sum lambda_i g_i (grad f + J^T lambda - z_L + z_U = 0).  x is the point
+    // x_state / x_ctrl publish.  The solver iterates on sf f and holds y as the multiplier of the
+    // unscaled row (the scaled row's times its row scale: the dual residual reads sf g + y - A^T y+),
+    // so what Ipopt's finalize_solution does with the row scales is already done and the objective
+    // scale alone remains: lambda = y / sf, z = z / sf.  64 lanes stride the record.
+    MPCG_HD void solution_out(double* s) const {
+        const int nx = 8 * N - 2, nc = 6 * N, t = wv.lane();
+        const double isf = 1.0 / (double)sf;
+        for (int e = t; e < nx; e += 64) {
+            int j, k;
+            if (e < nc) {
+                j = e / N;
+                k = e - j * N;
+            } else {
+                j = 6 + (e - nc) / (N - 1);
+                k = (e - nc) - (j - 6) * (N - 1);
+            }
+            s[e] = (double)(j < 6 ? x_state(j, k) : x_ctrl(j - 6, k));
+            s[nx + e] = (double)ld(L.ZL(k) + j) * isf;
+            s[2 * nx + e] = (double)ld(L.ZU(k) + j) * isf;
+        }
+        for (int e = t; e < nc; e += 64) {
+            const int j = e / N, k = e - j * N;
+            s[3 * nx + e] = (double)ld(L.Y(k) + j) * isf;
+        }
     }
 };
 

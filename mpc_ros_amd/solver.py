@@ -65,6 +65,41 @@ def _host_batch(state, coeffs, N, want_traj=True, diag=False):
     return B, out, ptrs
 
 
+def solution_elems(N: int) -> int:
+    """Doubles of one problem's solution record (mpcg_solution_elems): 3 (8N - 2) + 6N."""
+    return 3 * (8 * N - 2) + 6 * N
+
+
+def split_solution(sol, N: int) -> dict:
+    """Views of the records sol [..., solution_elems(N)] (numpy or torch): x, zl, zu [..., 8N-2] in
+    the reference's vars order and lam [..., 6N] in FG_eval's row order (include/mpcg.h)."""
+    nx = 8 * N - 2
+    assert sol.shape[-1] == solution_elems(N), "sol [..., 3 (8N - 2) + 6N]"
+    return dict(x=sol[..., :nx], zl=sol[..., nx:2 * nx], zu=sol[..., 2 * nx:3 * nx], lam=sol[..., 3 * nx:])
+
+
+def kkt(params, state, coeffs, sol, params_rows=None, base: str = "plugin", **ipopt) -> np.ndarray:
+    """The KKT certificate of the records sol on the host (mpcg_kkt: no GPU, no handle): cert [B, 4]
+    = stationarity, primal violation, complementarity (all unscaled, against MPC::Solve's own
+    bounds) and the objective.  params: a parameter map or an mpcg_params struct."""
+    p = params if isinstance(params, _lib.MpcgParams) else _params_struct(params, "fp64", ipopt, base)
+    state = np.ascontiguousarray(state, dtype=np.float64)
+    coeffs = np.ascontiguousarray(coeffs, dtype=np.float64)
+    sol = np.ascontiguousarray(sol, dtype=np.float64)
+    B = state.shape[0]
+    assert state.shape == (B, 6) and coeffs.shape == (B, 4) and sol.shape == (B, solution_elems(p.steps))
+    dp = C.POINTER(C.c_double)
+    rows = None
+    if params_rows is not None:
+        rows = np.ascontiguousarray(params_rows, dtype=np.float64)
+        assert rows.shape == (B, _lib.PP_FIELDS), "params_rows [B,16]"
+    cert = np.zeros((B, 4))
+    _lib.check(_lib.lib().mpcg_kkt(C.byref(p), B, state.ctypes.data_as(dp), coeffs.ctypes.data_as(dp),
+                                   rows.ctypes.data_as(dp) if rows is not None else None, sol.ctypes.data_as(dp),
+                                   cert.ctypes.data_as(dp)), "mpcg_kkt")
+    return cert
+
+
 def _on_device(t, shape, dtype="float64"):
     """t is a contiguous torch tensor of this dtype and shape on a GPU."""
     import torch
@@ -150,13 +185,27 @@ class BatchSolver:
         return int(_lib.lib().mpcg_handle_workspace_bytes(self._h, int(B)))
 
     # ----------------------------------------------------------------- solve
-    def solve(self, state: np.ndarray, coeffs: np.ndarray, want_traj: bool = True, params_rows=None) -> dict:
+    def solve(self, state: np.ndarray, coeffs: np.ndarray, want_traj: bool = True, params_rows=None,
+              want_solution: bool = False) -> dict:
         """params_rows [B, 16] (params.rows): a parameter row per problem instead of the handle's
-        per-problem fields (mpcg_solve_pp); a row outside the parameters' domains raises."""
+        per-problem fields (mpcg_solve_pp); a row outside the parameters' domains raises.
+        want_solution: also the full solution (mpcg_solve_sol) -- "sol" [B, solution_elems(N)] and
+        its views "x", "zl", "zu" [B, 8N-2] and "lam" [B, 6N] (split_solution)."""
         B, out, ptrs = _host_batch(state, coeffs, self.N, want_traj, diag=True)
+        rows = None
         if params_rows is not None:
             rows = np.ascontiguousarray(params_rows, dtype=np.float64)
             assert rows.shape == (B, _lib.PP_FIELDS), "params_rows [B,16]"
+        if want_solution:
+            dp = C.POINTER(C.c_double)
+            sol = np.zeros((B, solution_elems(self.N)))
+            _lib.check(_lib.lib().mpcg_solve_sol(self._h, B, ptrs[0], ptrs[1],
+                                                 rows.ctypes.data_as(dp) if rows is not None else None, *ptrs[2:],
+                                                 sol.ctypes.data_as(dp)), "mpcg_solve_sol")
+            out["sol"] = sol
+            out.update(split_solution(sol, self.N))
+            return out
+        if params_rows is not None:
             _lib.check(_lib.lib().mpcg_solve_pp(self._h, B, ptrs[0], ptrs[1], rows.ctypes.data_as(C.POINTER(C.c_double)),
                                                 *ptrs[2:]), "mpcg_solve_pp")
             return out
@@ -166,12 +215,13 @@ class BatchSolver:
         return out
 
     def solve_device(self, state, coeffs, u0, traj=None, status=None, obj=None, iters=None, stream=None, diag=None,
-                     pparams=None):
+                     pparams=None, sol=None):
         """All arguments are torch tensors on this handle's GPU (float64 / int32, contiguous);
         diag [B, 4] int32: restoration phases, filter overflows, parked, filter peak.
         pparams [B, 16] float64: a parameter row per problem (mpcg_solve_device_pp), read when the
         stream runs the solve -- keep it unchanged until then.  A row outside the parameters'
-        domains ends its problem with status 13, iters 0 and zero outputs."""
+        domains ends its problem with status 13, iters 0 and zero outputs.
+        sol [B, solution_elems(N)] float64: the full solution records (mpcg_solve_device_sol)."""
         import torch
 
         B = state.shape[0]
@@ -185,6 +235,13 @@ class BatchSolver:
         ptr, sp = _ptr, _stream_ptr(stream, state)
         if pparams is not None:
             _on_device(pparams, (B, _lib.PP_FIELDS))
+        if sol is not None:
+            _on_device(sol, (B, solution_elems(self.N)))
+            _lib.check(_lib.lib().mpcg_solve_device_sol(
+                self._h, B, ptr(state), ptr(coeffs), ptr(pparams), ptr(u0), ptr(traj), ptr(status), ptr(obj),
+                ptr(iters), ptr(diag), ptr(sol), sp), "mpcg_solve_device_sol")
+            return
+        if pparams is not None:
             _lib.check(_lib.lib().mpcg_solve_device_pp(
                 self._h, B, ptr(state), ptr(coeffs), ptr(pparams), ptr(u0), ptr(traj), ptr(status), ptr(obj),
                 ptr(iters), ptr(diag), sp), "mpcg_solve_device_pp")
@@ -192,6 +249,19 @@ class BatchSolver:
         _lib.check(_lib.lib().mpcg_solve_device_ex(
             self._h, B, ptr(state), ptr(coeffs), ptr(u0), ptr(traj), ptr(status), ptr(obj), ptr(iters), ptr(diag),
             sp), "mpcg_solve_device_ex")
+
+    def kkt_device(self, state, coeffs, sol, cert, pparams=None, stream=None):
+        """The KKT certificate of the records sol [B, solution_elems(N)] on the device
+        (mpcg_kkt_device): cert [B, 4] float64 = stationarity, primal violation, complementarity,
+        objective; the handle's parameters, or a row per problem (pparams [B, 16]; an invalid row
+        gives NaN).  Queued on the stream, no allocation."""
+        B = state.shape[0]
+        for t, shape in ((state, (B, 6)), (coeffs, (B, 4)), (sol, (B, solution_elems(self.N))), (cert, (B, 4))):
+            _on_device(t, shape)
+        if pparams is not None:
+            _on_device(pparams, (B, _lib.PP_FIELDS))
+        _lib.check(_lib.lib().mpcg_kkt_device(self._h, B, _ptr(state), _ptr(coeffs), _ptr(pparams), _ptr(sol),
+                                              _ptr(cert), _stream_ptr(stream, state)), "mpcg_kkt_device")
 
     # ------------------------------------------------ the benchmark's synthetic robots
     def synth_infinity_device(self, start: int, B: int, M: int = 11, seed: int | None = None, stream=None):
