@@ -209,7 +209,7 @@ __device__ __forceinline__ void pp_invalid_out(const WideArgs& a, int64_t p) {
 // (include/mpcg.h MPCG_PP_*), N, the model and the options from a.P; the row is loaded once by
 // scalar loads (pp_load_row), moved to VGPRs, checked before the solve (pp_invalid_out: no
 // trap) and applied from the same registers.
-template <int MODEL, bool SPLIT, class T, int NB, bool DEFOPT, bool WARM, bool PP = false>
+template <int MODEL, bool SPLIT, class T, int NB, bool DEFOPT, bool WARM, bool PP = false, bool RCK = false>
 __device__ __forceinline__ void solve_body(const WideArgs& a, const double* pparams = nullptr) {
     if ((int64_t)blockIdx.x >= a.B) return;
     const int64_t p = a.order ? (int64_t)a.order[blockIdx.x] : (int64_t)blockIdx.x;
@@ -236,7 +236,9 @@ __device__ __forceinline__ void solve_body(const WideArgs& a, const double* ppar
     }
     const int slot = claim_slot(a.slot_flags, a.nslots, a.nxcc, (int64_t)blockIdx.x);
     check_index_quiet(slot, a.nslots);
-    typedef WideSolver<DevWave, MODEL, SPLIT, T, NB> Solver;
+    // (RCK: the reciprocal slacks kept in registers -- WideSolver RCK -- in the instance the
+    // caller names; every other instance compiles as without them)
+    typedef WideSolver<DevWave, MODEL, SPLIT, T, NB, false, RCK> Solver;
     Solver S(Pk, pr, wv, (T*)a.slots + (int64_t)slot * a.slot_elems);
     if constexpr (WARM) {
         const float* h = a.handoff + p * a.handoff_stride;
@@ -294,7 +296,12 @@ __device__ __forceinline__ void solve_body(const WideArgs& a, const double* ppar
 
 template <int MODEL, bool SPLIT, class T, int NB, bool DEFOPT = false, int WPE = 2>
 __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE, WPE))) k_solve_wide(WideArgs a) {
-    solve_body<MODEL, SPLIT, T, NB, DEFOPT, false>(a);
+    // The kept reciprocal slacks: the diff-drive's two-wavefronts-per-SIMD instance with the default
+    // options as constants (the benchmark's), where they measured as a gain and 16 more VGPRs
+    // fit without a spill.  Measured without a gain: the bicycle's twin (251 VGPRs) and the
+    // one-wavefront instance of small batches; the instances with the options or a parameter
+    // row in registers spill with them.
+    solve_body<MODEL, SPLIT, T, NB, DEFOPT, false, false, DEFOPT && MODEL == 0 && WPE == 2>(a);
 }
 // the fp64 phase of the fp32 configuration (mpcg_params.precision 1): every problem again, from
 // the fp32 solver's converged iterate (WideSolver::solve_warm) or, where the fp32 solve did not
@@ -460,7 +467,7 @@ template <int MODEL, bool SPLIT, class T, int NB>
 __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 1))) k_resume_wide(WideArgs a) {
     const int t = threadIdx.x;
     const WideLayout Lw(a.P.N, a.P.filter_cap, MODEL);
-    typedef WideSolver<DevWave, MODEL, SPLIT, T, NB> Solver;
+    typedef WideSolver<DevWave, MODEL, SPLIT, T, NB, false, false> Solver;  // (RCK: no registers to spare here)
     for (;;) {
         int64_t p;
         T* ent;
@@ -511,7 +518,7 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 1)))
 k_resume_wide_pp(WideArgs a, const double* pparams) {
     const int t = threadIdx.x;
     const WideLayout Lw(a.P.N, a.P.filter_cap, MODEL);
-    typedef WideSolver<DevWave, MODEL, SPLIT, T, NB> Solver;
+    typedef WideSolver<DevWave, MODEL, SPLIT, T, NB, false, false> Solver;  // (RCK: no registers to spare here)
     for (;;) {
         int64_t p;
         T* ent;

@@ -36,7 +36,7 @@
 #include "ipm_core.h"
 
 #ifndef MPCG_FUSE
-#define MPCG_FUSE 3
+#define MPCG_FUSE 15
 #endif
 
 namespace mpcg {
@@ -206,8 +206,28 @@ MPCG_NOINLINE RestoOut resto_phase(const IpmParams& P, IpmProblem<T> pr, WV wv, 
 // block loops for any N <= 128.  A separate instantiation, called out of line from the
 // original problem's line search (resto_phase below): the main kernel's register
 // allocation does not see it.
-template <class WV, int MODEL = 0, bool SPLIT = false, class TT = double, int NB = 1, bool RESTO = false>
-struct WideSolver {
+// The registers of the kept reciprocal slacks (WideSolver FUSE_RC): members of the instances
+// that keep them only, so that a solver object that lives in the private segment (the resume
+// kernels') does not grow with them.
+template <class T, bool ON>
+struct RcRegs {
+    T rc_l[4] = {0, 0, 0, 0}, rc_u[4] = {0, 0, 0, 0};
+    int rc_ok = 0;
+};
+template <class T>
+struct RcRegs<T, false> {};
+template <bool SPLIT, class T, bool RCK>
+constexpr bool wide_fuse_rc() {
+    return SPLIT && sizeof(T) == 8 && RCK && (MPCG_FUSE & 5) == 5;
+}
+
+// RCK: the fp64 split solver keeps the reciprocal slacks of the statistics sweep in registers
+// for the step statistics (FUSE_RC below: 16 VGPRs held across the Riccati sweep).  A choice of
+// the instance: the kernels that have the registers take it (mpcg_wide_kern.h), the others
+// form the reciprocals again as before.
+template <class WV, int MODEL = 0, bool SPLIT = false, class TT = double, int NB = 1, bool RESTO = false,
+          bool RCK = true>
+struct WideSolver : RcRegs<TT, wide_fuse_rc<SPLIT, TT, RCK>()> {
     static_assert(NB == 1 || !SPLIT, "the half-wave split is for N <= 32");
     static_assert(!RESTO || !SPLIT, "the restoration problem runs the unsplit sweeps");
     typedef TT T;
@@ -277,7 +297,9 @@ struct WideSolver {
     T c_sa = 0, c_ca = 0;
     int c_ok = 0;
     // SPLIT, fused sweeps (MPCG_FUSE: bit 0 the stage data, bit 1 the accepted trial point's
-    // sums; 0 keeps the separate passes -- tests/native/wide_fused_check.cpp compares the two).
+    // sums, bit 2 the reciprocal slacks kept for the step statistics, bit 3 the accept pass in the
+    // split mapping that shares them; 0 keeps the separate passes
+    // -- tests/native/wide_fused_check.cpp and wide_slack_check.cpp compare the settings).
     // FUSE_SQ: the statistics sweep also writes the Newton system's SQD / SQV of its lane's four
     // variables (precompute_split's mode 0 with delta_w = 0 at the current mu: it holds every
     // operand), and sq_ok records that the stage table holds them for the iterate in LDS and
@@ -295,6 +317,34 @@ struct WideSolver {
     int sq_ok = 0;
     MPCG_HD void sq_drop() {
         if constexpr (FUSE_SQ) sq_ok = 0;
+    }
+    // FUSE_RC (bit 2, with bit 0): the reciprocal slacks rcp(w - lo), rcp(hi - w) of the lane's
+    // four variables (lane k: variables 0..3 of stage k, lane 32 + k: 4..7), kept in registers
+    // from the statistics sweep, whose sq_terms forms them, for the step statistics of the same
+    // iterate (step_stats_split), which would form them again from bitwise the same operands.
+    // They depend on the iterate alone -- not on mu, not on delta_w -- so a barrier update and an
+    // inertia-correction retry leave them valid; rc_ok (wave-uniform) is cleared wherever the
+    // iterate in LDS is replaced other than by the statistics sweep's accept pass (iter_drop()).
+    // Not part of a park entry: a resumed problem starts with rc_ok clear.
+    static constexpr bool FUSE_RC = wide_fuse_rc<SPLIT, TT, RCK>();  // (rc_l, rc_u, rc_ok: RcRegs)
+    // FUSE_AC (bit 3, with FUSE_RC): the accept pass in the split mapping (accept_split): each
+    // lane accepts its own four variables and its y rows, takes the old iterate's reciprocals
+    // from the registers, and the pair clamp_z's formula forms at the new iterate becomes the
+    // kept pair, which the statistics that follow in the same sweep take instead of forming it.
+    static constexpr bool FUSE_AC = FUSE_RC && (MPCG_FUSE & 8) != 0;
+    MPCG_HD void rc_drop() {
+        if constexpr (FUSE_RC) this->rc_ok = 0;
+    }
+    MPCG_HD bool rc_held() const {
+        if constexpr (FUSE_RC)
+            return this->rc_ok != 0;
+        else
+            return false;
+    }
+    // the iterate in LDS is replaced: neither the stage table nor the reciprocal slacks hold for it
+    MPCG_HD void iter_drop() {
+        sq_drop();
+        rc_drop();
     }
     static constexpr int model = MODEL;
     T lf;  // model 1: wheelbase
@@ -629,6 +679,79 @@ struct WideSolver {
         }
     }
 
+    // The accept pass in the split mapping (FUSE_AC): accept_one's and clamp_z's expressions on
+    // the lane's own four variables (lane k: 0..3 of stage k, lane 32 + k: 4..7) and y rows, with
+    // the old iterate's reciprocal slacks from the registers where they hold (rc_ok) and the new
+    // iterate's left there.  (Own copies of the two bodies: accept_one and clamp_z stay as they
+    // are for every other caller.)
+    // zlo, zuo, yo: the lane's accepted multipliers, which the statistics then need not load
+    MPCG_HD void accept_split(bool acc, T alpha, T amax_z, T* zlo, T* zuo, T* yo) {
+        const int t = wv.lane();
+        wv.sync();
+        if constexpr (FUSE_AC) {
+            if (acc) {
+                const bool have = wv.uni(rc_held());
+                const int k = t & 31;
+                const bool hi = t >= 32, last = k == N - 1;
+                if (k < N) {
+                    const int j0 = hi ? 4 : 0, nv = (last && hi) ? 2 : 4, nr = hi ? 2 : 4;
+                    T w[4], dw[4], zl[4], zu[4];
+                    ldv<4>(L.W(k) + j0, w);
+                    ldv<4>(L.DW(k) + j0, dw);
+                    ldv<4>(L.ZL(k) + j0, zl);
+                    ldv<4>(L.ZU(k) + j0, zu);
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) {
+                        if (q < nv) {
+                            const T lo = q < 2 ? sl : (q == 2 ? (hi ? wl : sl) : (hi ? al : sl));
+                            const T hb = q < 2 ? su : (q == 2 ? (hi ? wu : su) : (hi ? au : su));
+                            T rdl, rdu;
+                            if (have) {
+                                rdl = opaque(this->rc_l[q]);
+                                rdu = opaque(this->rc_u[q]);
+                            } else {
+                                rdl = rcp(w[q] - lo);
+                                rdu = rcp(hb - w[q]);
+                            }
+                            const T dzl = mu * rdl - zl[q] - zl[q] * rdl * dw[q];
+                            const T dzu = mu * rdu - zu[q] + zu[q] * rdu * dw[q];
+                            const T wn = w[q] + alpha * dw[q];
+                            const T a = zl[q] + amax_z * dzl, b = zu[q] + amax_z * dzu;
+                            const T ksig = (T)1e10, iksig = (T)1e-10;
+                            const T rs2 = rcp(wn - lo), ru2 = rcp(hb - wn);
+                            zl[q] = tmax(tmin(a, ksig * mu * rs2), mu * rs2 * iksig);
+                            zu[q] = tmax(tmin(b, ksig * mu * ru2), mu * ru2 * iksig);
+                            w[q] = wn;
+                            this->rc_l[q] = rs2;
+                            this->rc_u[q] = ru2;
+                        }
+                    }
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) {
+                        st(L.W(k) + j0 + q, w[q]);
+                        st(L.ZL(k) + j0 + q, zl[q]);
+                        st(L.ZU(k) + j0 + q, zu[q]);
+                    }
+                    T y[4], yp[4];  // (upper half: y4, y5 and two entries it leaves alone)
+                    ldv<4>(L.Y(k) + j0, y);
+                    ldv<4>(L.YP(k) + j0, yp);
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) {
+                        if (q < nr) {
+                            y[q] = y[q] + alpha * (yp[q] - y[q]);
+                            st(L.Y(k) + j0 + q, y[q]);
+                        }
+                        zlo[q] = zl[q];
+                        zuo[q] = zu[q];
+                        yo[q] = y[q];
+                    }
+                }
+                this->rc_ok = 1;
+            }
+        }
+        wv.sync();
+    }
+
     // Statistics of the iterate (SPLIT): lane k of the lower half-wave takes stage k's
     // variables 0..3, dynamics rows 0..3 and the heading theta, lane 32 + k the variables
     // 4..7, rows 4, 5 and the heading error; the one Jacobian entry the lower half needs
@@ -637,8 +760,12 @@ struct WideSolver {
     // written by the half-wave that computes them.
     MPCG_HD void stats_split(bool acc, T alpha, T amax_z) {
         const int t = wv.lane();
-        accept_all(t, acc, alpha, amax_z);
-        wv.mark(16);
+        T azl[4] = {0, 0, 0, 0}, azu[4] = {0, 0, 0, 0}, ay[4] = {0, 0, 0, 0};
+        if constexpr (FUSE_AC)
+            accept_split(acc, alpha, amax_z, azl, azu, ay);
+        else
+            accept_all(t, acc, alpha, amax_z);
+        wv.mark(FUSE_AC && acc ? 21 : 16);  // (21: the split accept pass, whose reciprocals the statistics take)
         const bool reuse = acc && c_ok;  // (uniform)
         c_ok = 0;
         // the trial sweep reduced the objective, log-barrier and violation sums at this point
@@ -655,9 +782,18 @@ struct WideSolver {
         T twk = dt, tvk = 0, f1 = 0;
         if (act) {
             ldn<8>(L.W(k), w);
-            ldv<4>(L.ZL(k) + j0, zl);
-            ldv<4>(L.ZU(k) + j0, zu);
-            ldv<4>(L.Y(k) + j0, yq);  // (upper half: y4, y5 and two unused entries)
+            if (FUSE_AC && acc) {  // (uniform: the accept pass left them in this lane's registers)
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    zl[q] = azl[q];
+                    zu[q] = azu[q];
+                    yq[q] = ay[q];
+                }
+            } else {
+                ldv<4>(L.ZL(k) + j0, zl);
+                ldv<4>(L.ZU(k) + j0, zu);
+                ldv<4>(L.Y(k) + j0, yq);  // (upper half: y4, y5 and two unused entries)
+            }
             const int sb = L.ST(k);
             T cv[3] = {0, 0, 0};
             if (!last) {
@@ -795,7 +931,22 @@ struct WideSolver {
                         // variable: precompute_split's expressions, mode 0, delta_w = 0
                         const T gq = opaque(hi ? (q == 0 ? g4 : (q == 1 ? g5 : gu[q - 2])) : (q == 3 ? g3 : (T)0));
                         const T hq = hi ? (q < 2 ? hess_state(4 + q) : hess_ctrl(k, q - 2)) : hess_state(q);
-                        sq_terms(hq, gq, wq - lo, hb - wq, zl[q], zu[q], &sqd[q], &sqv[q]);
+                        bool took = false;
+                        if constexpr (FUSE_AC) {
+                            if (acc) {  // (uniform: the accept pass of this sweep left the pair)
+                                sq_terms_r(hq, gq, opaque(this->rc_l[q]), opaque(this->rc_u[q]), zl[q], zu[q], &sqd[q],
+                                           &sqv[q]);
+                                took = true;
+                            }
+                        }
+                        if (!took) {
+                            T rl, ru;
+                            sq_terms(hq, gq, wq - lo, hb - wq, zl[q], zu[q], &sqd[q], &sqv[q], &rl, &ru);
+                            if constexpr (FUSE_RC) {
+                                this->rc_l[q] = rl;
+                                this->rc_u[q] = ru;
+                            }
+                        }
                     }
                 }
             }
@@ -810,6 +961,7 @@ struct WideSolver {
             }
         }
         if constexpr (FUSE_SQ) sq_ok = 1;
+        if constexpr (FUSE_RC) this->rc_ok = 1;
         // (max |z s| = max(max z s, -min z s): one reduction fewer)
         if (sums_known) {
             T v[7] = {pinf, puns, dinf, mn, mx, ly, lz};
@@ -1198,8 +1350,15 @@ struct WideSolver {
     // The barrier Hessian diagonal (without delta_w) and the barrier gradient of one variable
     // with slacks dl, du (mode 0): one body for precompute_split and for the statistics sweep
     // that writes the same entries (FUSE_SQ).  qd > 0, so adding delta_w = 0 changes no bit.
-    MPCG_HD void sq_terms(T hq, T gq, T dl, T du, T zl, T zu, T* qd, T* qv) const {
+    // The reciprocal slacks come out as well (*rl, *ru): the statistics sweep keeps them (FUSE_RC).
+    MPCG_HD void sq_terms(T hq, T gq, T dl, T du, T zl, T zu, T* qd, T* qv, T* rl, T* ru) const {
         const T rdl = rcp(dl), rdu = rcp(du);
+        sq_terms_r(hq, gq, rdl, rdu, zl, zu, qd, qv);
+        *rl = rdl;
+        *ru = rdu;
+    }
+    // (with the reciprocal slacks given)
+    MPCG_HD void sq_terms_r(T hq, T gq, T rdl, T rdu, T zl, T zu, T* qd, T* qv) const {
         *qd = sf * hq + zl * rdl + zu * rdu;
         *qv = sf * gq - mu * rdl + mu * rdu;
     }
@@ -1265,7 +1424,8 @@ struct WideSolver {
                 const T lo = q < 2 ? sl : (q == 2 ? (hi ? wl : sl) : (hi ? al : sl));
                 const T hb = q < 2 ? su : (q == 2 ? (hi ? wu : su) : (hi ? au : su));
                 if (mode == 0) {
-                    sq_terms(hq, gq, w[q] - lo, hb - w[q], zl[q], zu[q], &qd, &qv);
+                    T rl, ru;  // (not kept: the statistics sweep is the one producer)
+                    sq_terms(hq, gq, w[q] - lo, hb - w[q], zl[q], zu[q], &qd, &qv, &rl, &ru);
                     qd += delta_w;
                 } else {
                     qd = 1;
@@ -1618,11 +1778,25 @@ struct WideSolver {
         const T dq[4] = {hi ? xk[4] : xk[0], hi ? xk[5] : xk[1], hi ? duk[0] : xk[2], hi ? duk[1] : xk[3]};
         const T lo2 = hi ? wl : sl, hi2 = hi ? wu : su, lo3 = hi ? al : sl, hi3 = hi ? au : su;
         const int nv = (last && hi) ? 2 : 4;
+        // (FUSE_RC: the statistics sweep of this iterate formed the same reciprocals in this lane)
+        const bool rc_have = FUSE_RC && wv.uni(rc_held());
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
             if (q < nv) {
                 const T lo = q < 2 ? sl : (q == 2 ? lo2 : lo3), up_ = q < 2 ? su : (q == 2 ? hi2 : hi3);
-                const T rdl = rcp(w[q] - lo), rdu = rcp(up_ - w[q]);
+                T rdl, rdu;
+                bool took = false;
+                if constexpr (FUSE_RC) {
+                    if (rc_have) {
+                        rdl = this->rc_l[q];
+                        rdu = this->rc_u[q];
+                        took = true;
+                    }
+                }
+                if (!took) {
+                    rdl = rcp(w[q] - lo);
+                    rdu = rcp(up_ - w[q]);
+                }
                 const T gphi = gq[q] - mu * rdl + mu * rdu;
                 dir_var_r(w[q], zl[q], zu[q], lo, up_, gphi, dq[q], rdl, rdu, F);
             }
@@ -1799,6 +1973,9 @@ struct WideSolver {
         wv.mark(4);
         Fwd F{(T)1, (T)1, (T)0, (T)0};
         if constexpr (SPLIT) {
+            // (the reciprocal slacks kept / formed again; 20: no step statistics.  One call without a
+            // branch of its own: a separate test of mode here changed the kernel's register allocation)
+            wv.mark(mode != 0 ? 20 : (rc_held() ? 18 : 19));
             if (mode == 0 && ks < N) step_stats_split(ks, xk, duk, F);
         } else if (t < N) {
             const int k = t;
@@ -3666,7 +3843,7 @@ struct WideSolver {
         mu = wv.uni_d(mu0);
         tau = wv.uni_d(tmax((T)0.99, (T)1 - mu0));
         status = 0;
-        sq_drop();  // (init: the least-squares solve, mode 1; init_warm: a statistics sweep first)
+        iter_drop();  // (init: the least-squares solve, mode 1; init_warm: a statistics sweep first)
         theta_max() = -1;
         theta_min = -1;
         dw_last = 0;
@@ -4064,7 +4241,7 @@ struct WideSolver {
         xcopy(false, WideLayout::XP, 0, 36);
         wd_short = 0;
         c_ok = 0;
-        sq_drop();  // (the iterate is replaced; its statistics sweep writes the table again)
+        iter_drop();  // (the iterate is replaced; its statistics sweep writes the table again)
         return do_stats(false, (T)0, (T)0, K_WD_STATS);
     }
     MPCG_HD int k_wd_stats() {
@@ -4103,7 +4280,7 @@ struct WideSolver {
         // the iterate moved behind the stage table.  (No Newton system is solved before the next
         // statistics sweep: an accepted soft step goes on to one, a rejected one -- rec_in of the
         // kept iterate in k_soft_pd1 -- ends the line search in ls_fail.)
-        sq_drop();
+        iter_drop();
         return set_op(OP_PDERR, K_SOFT_PD1);
     }
     MPCG_HD int k_soft_pd1() {
@@ -4114,6 +4291,7 @@ struct WideSolver {
         rec_in<0, 24>(L.SP_SOFT());
         spill_in(L.SP_SOFT() + 3 * WideLayout::WS * N, L.Y(0), WideLayout::YS * N);
         xcopy(false, WideLayout::XP, 48, 24);
+        iter_drop();  // (the kept iterate is back; both records were dropped with the step in k_soft_pd0)
         return soft_done(false, false);
     }
     MPCG_HD int soft_done(bool accept, bool sat) {
@@ -4167,7 +4345,7 @@ struct WideSolver {
             if (wv.uni(theta <= (T)1e-2 * (T)P.tol)) {
                 if (have_acc) {
                     rec_in<0, 8>(L.SP_ACC());  // (the solve ends here: the stage table is not read again)
-                    sq_drop();
+                    iter_drop();
                     return IPM_ACCEPTABLE;
                 }
                 return IPM_RESTORATION_FAILURE;
@@ -4213,7 +4391,7 @@ struct WideSolver {
         iter = wv.uni(o.iter);
         n_fover += wv.uni(o.fover);
         c_ok = 0;
-        sq_drop();  // (a new iterate comes back; its statistics sweep writes the table again)
+        iter_drop();  // (a new iterate comes back; its statistics sweep writes the table again)
         const int s = wv.uni(o.status);
         if (s) return s;
         clamp_all();
@@ -4554,7 +4732,7 @@ struct WideSolver {
         nf_peak = wv.uni((int)src[26]);
         status = NEED_RESTO;
         c_ok = 0;
-        sq_drop();  // (not parked: the restoration phase this solver continues with replaces the iterate)
+        iter_drop();  // (not parked: the restoration phase this solver continues with replaces the iterate)
         acc_pending = false;
         cur_acceptable = false;
     }

@@ -19,12 +19,14 @@
 #include "wide_core.h"
 
 namespace mpcg {
-constexpr int NPH = 18;
+constexpr int NPH = 22;
 // stats: the statistics sweep after the accept pass (accept); ric-pre: the Riccati sweep's setup
 // after the stage-data pass (sq-run; sq-skip: the pass skipped, the table written by the
 // statistics sweep); 9..13: the continuations between sweeps
 const char* kPhase[NPH] = {"stats", "ric-pre", "ric-sweep", "fwd-seq", "fwd-adj", "fwd-par", "trial", "ls-rest", "begin-rest",
-                           "pre-trial", "accept-chk", "newton-in", "setref", "step-out", "sq-skip", "sq-run", "accept", "pre-kbt"};
+                           "pre-trial", "accept-chk", "newton-in", "setref", "step-out", "sq-skip", "sq-run", "accept", "pre-kbt",
+                           // (forward()'s mark before the step statistics: the reciprocal slacks kept / formed / no step statistics)
+                           "rc-kept", "rc-formed", "fwd-mode1", "accept-spl"};
 
 struct ProfWave : DevWaveBase {
     unsigned long long* acc;
