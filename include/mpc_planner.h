@@ -59,6 +59,13 @@ class MPC {
     // copies nothing more; empty until a Solve has run with it on.
     void keep_solution(bool on) { _keep_solution = on; }
     const vector<double>& solution() const { return _solution; }
+    // The feedback law around the last Solve's solution (include/mpcg.h mpcg_sens, evaluated on the
+    // host from the kept record): 2 x 10 doubles, row-major, d(w0, a0) / d(state[0..5], coeffs[0..3]);
+    // u = clip(u0 + gain [dstate; dcoeffs]) corrects the command for a measured state that differs
+    // from the predicted one without another Solve.  Needs keep_solution(true); empty before such a
+    // Solve.  gain_info(): mpcg_sens's flag (0 valid; 1, 2: the gain is NaN), -1 before such a Solve.
+    const vector<double>& feedback_gain() const { return _gain; }
+    int gain_info() const { return _gain_info; }
     // GPU the solver runs on (default 0); call before the first Solve.
     void set_device(int device) { _device = device; }
 
@@ -78,6 +85,8 @@ class MPC {
     double _last_obj;
     bool _keep_solution = false;
     vector<double> _solution;
+    vector<double> _gain;
+    int _gain_info = -1;
 };
 
 #endif /* MPCG_MPC_PLANNER_H */

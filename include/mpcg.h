@@ -513,6 +513,51 @@ int mpcg_kkt(const mpcg_params* p, int64_t B, const double* state, const double*
 int mpcg_kkt_device(mpcg_handle* h, int64_t B, const double* d_state, const double* d_coeffs, const double* d_pparams,
                     const double* d_sol, double* d_cert, void* stream);
 
+/* ---- Sensitivities of the solution ----
+ * The first-order feedback law around a solution record: gain [B][2][10] (row-major) =
+ * d(omega_0, a_0) / d(state[0..5], coeffs[0..3]), from the NLP and the record alone (no solver
+ * code, no scaling).  With W the Hessian in x of f + sum lambda_i g_i at the record's x, J the
+ * Jacobian of g, r_i = min(constr_viol_tol, bound_relax_factor max(1, |bound_i|)) the solver's
+ * bound relaxation and Sigma = diag(zl_i / (x_i - (xl_i - r_i)) + zu_i / ((xu_i + r_i) - x_i))
+ * (xl, xu MPC::Solve's original bounds), it solves for ten right-hand sides
+ *     [ W + Sigma  J^T ] [ dx      ]   [ a_c ]
+ *     [ J          0   ] [ dlambda ] = [ b_c ]
+ *   c = 0..5, state component s: a = 0, b = the unit vector of row s N (the initial-state row);
+ *   c = 6..9, coefficient c_i:   b[4N + k + 1] = x_k^i and a[x_k] = i x_k^(i-1) lambda[4N + k + 1]
+ *                                for k = 0..N-2 (the polynomial enters the cte rows only)
+ * by one backward Riccati sweep over the stages (the state augmented with the previous control)
+ * and one forward sweep.  gain[r][c] = dx_c[6N] (r = 0) and dx_c[7N - 1] (r = 1).  No thresholding:
+ * where u0 sits at its bound the row is about 1e-7, not exactly 0.  Meaningful where the solve
+ * ended with status 1 or 4; the status is not looked at.
+ *   dx   [B][10][8N-2] or NULL: the full primal columns in the record's variable order
+ *   info [B] int32 or NULL:
+ *     0  gain valid
+ *     1  a stage's reduced control Hessian R + B^T P B was not positive definite: the KKT matrix
+ *        does not have inertia (8N-2, 6N); gain and dx are NaN
+ *     2  a parameter row outside mpcg_pparams_check's domains, a non-finite record entry or
+ *        coefficient, or a slack <= 0 (x outside its relaxed bound); gain and dx are NaN
+ * pparams: as in mpcg_kkt.  state is not read (the gain does not depend on the bound of the
+ * initial-state rows); it is in the signature for symmetry with mpcg_kkt and may be NULL.
+ * mpcg_sens: host arrays, no GPU and no handle (the kernel's code with the 64 lanes in a loop).
+ * mpcg_sens_device: device arrays, one problem per wavefront, the work area in LDS at every
+ * horizon (2 <= N <= 128), queued on `stream`; no solver state, no workspace, no atomics, no
+ * allocation, capturable; nothing traps.  Host and device agree to rounding (sin / cos).
+ * Refused (-1) before any launch: a NULL sol or gain; precision 1 with rows. */
+#define MPCG_SENS_COLS 10
+int mpcg_sens(const mpcg_params* p, int64_t B, const double* state, const double* coeffs, const double* pparams,
+              const double* sol, double* gain, double* dx, int32_t* info);
+int mpcg_sens_device(mpcg_handle* h, int64_t B, const double* d_state, const double* d_coeffs, const double* d_pparams,
+                     const double* d_sol, double* d_gain, double* d_dx, int32_t* d_info, void* stream);
+/* The correction without a solve (the advanced-step correction of a delay-mode prediction):
+ * u[b] = clip(u0[b] + gain[b] [dstate[b]; dcoeffs[b]]) to +-ANGVEL, +-MAXTHR (the row's if pparams
+ * is given; dcoeffs may be NULL = 0); a sum that is not finite (a NaN gain) gives u = u0.
+ * u0, u [B][2], dstate [B][6], dcoeffs [B][4].  mpcg_sens_apply: the rule as a pure host function;
+ * mpcg_sens_apply_device: one robot per lane, queued on `stream`, bitwise the host rule. */
+int mpcg_sens_apply(const mpcg_params* p, int64_t B, const double* pparams, const double* gain, const double* u0,
+                    const double* dstate, const double* dcoeffs, double* u);
+int mpcg_sens_apply_device(mpcg_handle* h, int64_t B, const double* d_pparams, const double* d_gain, const double* d_u0,
+                           const double* d_dstate, const double* d_dcoeffs, double* d_u, void* stream);
+
 /* The benchmark's synthetic robots (the "infinity set", mpc_ros_amd/infinity.py) generated on
  * the device: robot start + i of the set (i < B) is a pure function of (seed, start + i) --
  * a pose near a lemniscate course, its speed and previous controls, and a plan of M waypoints

@@ -98,6 +98,12 @@ SIGNATURES = {
     "mpcg_kkt": ([_PP, C.c_int64, _dp, _dp, _dp, _dp, _dp], C.c_int),
     "mpcg_kkt_device": ([C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                          C.c_void_p], C.c_int),
+    "mpcg_sens": ([_PP, C.c_int64, _dp, _dp, _dp, _dp, _dp, _dp, _ip], C.c_int),
+    "mpcg_sens_device": ([C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                          C.c_void_p, C.c_void_p, C.c_void_p], C.c_int),
+    "mpcg_sens_apply": ([_PP, C.c_int64, _dp, _dp, _dp, _dp, _dp, _dp], C.c_int),
+    "mpcg_sens_apply_device": ([C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                C.c_void_p, C.c_void_p], C.c_int),
     "mpcg_decelerate": ([C.c_double] * 6, C.c_double),
     "mpcg_track_device_goal": ([C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                 C.c_void_p, C.c_double, C.c_double, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
@@ -131,6 +137,7 @@ SIGNATURES = {
                                     C.c_void_p, C.c_void_p], C.c_int),
 }
 
+SENS_COLS = 10  # MPCG_SENS_COLS: columns of a gain (6 state components, 4 coefficients)
 PP_FIELDS = 16  # MPCG_PP_FIELDS: doubles per parameter row (their order: params.ROW_KEYS)
 
 STRATEGY = {"auto": 0, "lane": 1, "wave": 2}  # (LANE was removed in ABI 2: selecting it raises)

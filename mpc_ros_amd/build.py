@@ -13,12 +13,12 @@ ROOT = os.path.dirname(HERE)
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libmpcg.so")
 SOURCES = [os.path.join(CSRC, f) for f in ("mpcg_wide.hip", "mpcg_wide_inst.hip", "mpcg_track.hip", "mpcg_synth.hip",
-                                           "mpcg_kkt.hip",
+                                           "mpcg_kkt.hip", "mpcg_sens.hip",
                                            "mpcg_api.cpp", "mpcg_multi.cpp", "mpc_planner.cpp")]
 INST = os.path.join(CSRC, "mpcg_wide_inst.hip")
 N_INST = 20  # MPCG_INST groups of mpcg_wide_inst.hip (the instance lists of wide_plan.h)
 HEADERS = [os.path.join(CSRC, f) for f in ("ipm_core.h", "wide_core.h", "wide_plan.h", "wave_dev.h", "mpcg_internal.h",
-                                           "mpcg_wide_kern.h", "mpcg_pp.h", "mpcg_window.h", "mpcg_kkt.h")] + [
+                                           "mpcg_wide_kern.h", "mpcg_pp.h", "mpcg_window.h", "mpcg_kkt.h", "mpcg_sens.h")] + [
     os.path.join(ROOT, "include", f) for f in ("mpcg.h", "mpc_planner.h")]
 ARCH = os.environ.get("MPCG_OFFLOAD_ARCH", "gfx950")
 

@@ -38,7 +38,8 @@ MPC::MPC(const MPC& o)
       _y_start(o._y_start), _theta_start(o._theta_start), _v_start(o._v_start), _cte_start(o._cte_start),
       _etheta_start(o._etheta_start), _angvel_start(o._angvel_start), _a_start(o._a_start), _params(o._params),
       _device(o._device), _handle(nullptr), _last_status(o._last_status), _last_iters(o._last_iters),
-      _last_obj(o._last_obj), _keep_solution(o._keep_solution), _solution(o._solution) {}
+      _last_obj(o._last_obj), _keep_solution(o._keep_solution), _solution(o._solution),
+      _gain(o._gain), _gain_info(o._gain_info) {}
 
 MPC& MPC::operator=(const MPC& o) {
     if (this == &o) return *this;
@@ -65,6 +66,8 @@ MPC& MPC::operator=(const MPC& o) {
     _last_obj = o._last_obj;
     _keep_solution = o._keep_solution;
     _solution = o._solution;
+    _gain = o._gain;
+    _gain_info = o._gain_info;
     return *this;  // keeps its own GPU handle
 }
 
@@ -143,6 +146,18 @@ vector<double> MPC::SolveRaw(const double* state, const double* coeffs) {
     _last_status = status;
     _last_iters = iters;
     _last_obj = obj;
+    if (_keep_solution) {
+        // (one record: the sweeps on the host, a few microseconds at N = 20)
+        const mpcg_params p = effective_params();
+        int32_t info = -1;
+        _gain.assign(2 * MPCG_SENS_COLS, 0.0);
+        if (mpcg_sens(&p, 1, state, coeffs, nullptr, _solution.data(), _gain.data(), nullptr, &info) != 0) {
+            std::fprintf(stderr, "[MPC] feedback gain failed: %s\n", mpcg_last_error());
+            _gain.clear();
+            info = -1;
+        }
+        _gain_info = info;
+    }
     mpc_x.assign(traj.begin(), traj.begin() + N);
     mpc_y.assign(traj.begin() + N, traj.begin() + 2 * N);
     mpc_theta.assign(traj.begin() + 2 * N, traj.end());

@@ -13,6 +13,7 @@
 #include "mpcg.h"
 #include "mpcg_internal.h"
 #include "mpcg_kkt.h"
+#include "mpcg_sens.h"
 #include "mpcg_pp.h"
 #include "mpcg_window.h"
 
@@ -634,6 +635,80 @@ int mpcg_kkt_device(mpcg_handle* h, int64_t B, const double* d_state, const doub
     e = mpcg::launch_kkt_certify(B, P.N, P.model, mpcg::pp_row_pack(P), d_pparams, d_state, d_coeffs, d_sol, d_cert,
                                  (hipStream_t)stream);
     if (e != hipSuccess) return hip_fail(e, "kkt certificate launch");
+    return 0;
+}
+
+// ---- the feedback gains (mpcg_sens.h) ----
+int mpcg_sens(const mpcg_params* p, int64_t B, const double* state, const double* coeffs, const double* pparams,
+              const double* sol, double* gain, double* dx, int32_t* info) {
+    (void)state;  // (the gain does not depend on the bound of the initial-state rows)
+    if (!p) return fail(-1, "null params");
+    if (B < 0) return fail(-1, "negative batch");
+    if (!sol || !gain) return fail(-1, "sol and gain are required");
+    if (B == 0) return 0;
+    if (!coeffs) return fail(-1, "coeffs is required");
+    int rc = mpcg_params_check(p);
+    if (rc) return rc;
+    if (pparams && p->precision != 0) return fail(-1, kNoFp32Rows);
+    const mpcg::IpmParams P = to_ipm(*p);
+    const mpcg::PPRow row = mpcg::pp_row_pack(P);
+    const int64_t ne = mpcg::solution_elems(P.N), nx = 8 * (int64_t)P.N - 2;
+    std::vector<double> w((size_t)mpcg::sens_work_elems(P.N));
+    mpcg::SensHostLanes ex;
+    for (int64_t b = 0; b < B; ++b) {
+        const int e = mpcg::sens_problem(ex, w.data(), pparams ? pparams + b * MPCG_PP_FIELDS : row.f, P.model, P.N,
+                                         P.constr_viol_tol, P.bound_relax_factor, coeffs + b * 4, sol + b * ne,
+                                         gain + b * 2 * MPCG_SENS_COLS, dx ? dx + b * MPCG_SENS_COLS * nx : nullptr);
+        if (info) info[b] = e;
+    }
+    return 0;
+}
+
+int mpcg_sens_device(mpcg_handle* h, int64_t B, const double* d_state, const double* d_coeffs, const double* d_pparams,
+                     const double* d_sol, double* d_gain, double* d_dx, int32_t* d_info, void* stream) {
+    (void)d_state;
+    int rc = batch_check(h, B);
+    if (rc) return rc;
+    if (!d_sol || !d_gain) return fail(-1, "sol and gain are required");
+    if (B == 0) return 0;
+    if (!d_coeffs) return fail(-1, "coeffs is required");
+    rc = mpcg_params_check(&h->params);
+    if (rc) return rc;
+    if (d_pparams && h->params.precision != 0) return fail(-1, kNoFp32Rows);
+    if (h->params.steps > 128) return fail(-1, "STEPS must be <= 128");
+    hipError_t e = hipSetDevice(h->device);
+    if (e != hipSuccess) return hip_fail(e, "hipSetDevice");
+    const mpcg::IpmParams P = handle_ipm(h);
+    // (the work area is the kernel's LDS at every horizon: no handle scratch, nothing to order)
+    e = mpcg::launch_sens(B, P.N, P.model, mpcg::pp_row_pack(P), P.constr_viol_tol, P.bound_relax_factor, d_pparams,
+                          d_coeffs, d_sol, d_gain, d_dx, d_info, (hipStream_t)stream);
+    if (e != hipSuccess) return hip_fail(e, "sensitivity launch");
+    return 0;
+}
+
+int mpcg_sens_apply(const mpcg_params* p, int64_t B, const double* pparams, const double* gain, const double* u0,
+                    const double* dstate, const double* dcoeffs, double* u) {
+    if (!p) return fail(-1, "null params");
+    if (B < 0) return fail(-1, "negative batch");
+    if (B == 0) return 0;
+    if (!gain || !u0 || !dstate || !u) return fail(-1, "gain, u0, dstate and u are required");
+    const mpcg::PPRow row = mpcg::pp_row_pack(to_ipm(*p));
+    for (int64_t b = 0; b < B; ++b)
+        mpcg::sens_apply(pparams ? pparams + b * MPCG_PP_FIELDS : row.f, gain + b * 2 * MPCG_SENS_COLS, u0 + b * 2,
+                         dstate + b * 6, dcoeffs ? dcoeffs + b * 4 : nullptr, u + b * 2);
+    return 0;
+}
+
+int mpcg_sens_apply_device(mpcg_handle* h, int64_t B, const double* d_pparams, const double* d_gain, const double* d_u0,
+                           const double* d_dstate, const double* d_dcoeffs, double* d_u, void* stream) {
+    int rc = batch_check(h, B);
+    if (rc || B == 0) return rc;
+    if (!d_gain || !d_u0 || !d_dstate || !d_u) return fail(-1, "gain, u0, dstate and u are required");
+    hipError_t e = hipSetDevice(h->device);
+    if (e != hipSuccess) return hip_fail(e, "hipSetDevice");
+    e = mpcg::launch_sens_apply(B, mpcg::pp_row_pack(handle_ipm(h)), d_pparams, d_gain, d_u0, d_dstate, d_dcoeffs, d_u,
+                                (hipStream_t)stream);
+    if (e != hipSuccess) return hip_fail(e, "sensitivity apply launch");
     return 0;
 }
 

@@ -44,6 +44,14 @@ hipError_t launch_wide_solve(const IpmParams& P, int64_t B, const double* state,
 struct PPRow;
 hipError_t launch_kkt_certify(int64_t B, int N, int model, const PPRow& row, const double* rows, const double* state,
                               const double* coeffs, const double* sol, double* cert, hipStream_t stream);
+// The feedback gains (mpcg_sens.hip): gain [B][2][10], dx [B][10][8N-2] (or null) and info [B] (or
+// null) at the records sol; cvt, brf: the handle's constr_viol_tol and bound_relax_factor.  And the
+// correction u = clip(u0 + gain [dstate; dcoeffs]) (dcoeffs or null), one robot per lane.
+hipError_t launch_sens(int64_t B, int N, int model, const PPRow& row, double cvt, double brf, const double* rows,
+                       const double* coeffs, const double* sol, double* gain, double* dx, int32_t* info,
+                       hipStream_t stream);
+hipError_t launch_sens_apply(int64_t B, const PPRow& row, const double* rows, const double* gain, const double* u0,
+                             const double* dstate, const double* dcoeffs, double* u, hipStream_t stream);
 // Solve order (expected-longest first): device buffer bytes for B problems, and the
 // launch that writes the workgroup -> problem map into `buf` (returned in *order).
 size_t wide_sched_bytes(int64_t B);

@@ -100,6 +100,56 @@ def kkt(params, state, coeffs, sol, params_rows=None, base: str = "plugin", **ip
     return cert
 
 
+def sens(params, state, coeffs, sol, params_rows=None, want_dx: bool = False, base: str = "plugin", **ipopt) -> dict:
+    """The feedback gains of the records sol on the host (mpcg_sens: no GPU, no handle): "gain"
+    [B, 2, 10] = d(omega_0, a_0) / d(state, coeffs), "info" [B] int32 (0 valid, 1 wrong inertia, 2
+    invalid row or record; gain is NaN for 1 and 2) and, with want_dx, "dx" [B, 10, 8N-2], the full
+    primal columns.  params: a parameter map or an mpcg_params struct (constr_viol_tol and
+    bound_relax_factor are the relaxation of the slacks)."""
+    p = params if isinstance(params, _lib.MpcgParams) else _params_struct(params, "fp64", ipopt, base)
+    state = np.ascontiguousarray(state, dtype=np.float64)
+    coeffs = np.ascontiguousarray(coeffs, dtype=np.float64)
+    sol = np.ascontiguousarray(sol, dtype=np.float64)
+    B = state.shape[0]
+    assert state.shape == (B, 6) and coeffs.shape == (B, 4) and sol.shape == (B, solution_elems(p.steps))
+    dp = C.POINTER(C.c_double)
+    rows = None
+    if params_rows is not None:
+        rows = np.ascontiguousarray(params_rows, dtype=np.float64)
+        assert rows.shape == (B, _lib.PP_FIELDS), "params_rows [B,16]"
+    out = dict(gain=np.zeros((B, 2, _lib.SENS_COLS)), info=np.zeros(B, dtype=np.int32))
+    if want_dx:
+        out["dx"] = np.zeros((B, _lib.SENS_COLS, 8 * p.steps - 2))
+    _lib.check(_lib.lib().mpcg_sens(C.byref(p), B, state.ctypes.data_as(dp), coeffs.ctypes.data_as(dp),
+                                    rows.ctypes.data_as(dp) if rows is not None else None, sol.ctypes.data_as(dp),
+                                    out["gain"].ctypes.data_as(dp), out["dx"].ctypes.data_as(dp) if want_dx else None,
+                                    out["info"].ctypes.data_as(C.POINTER(C.c_int32))), "mpcg_sens")
+    return out
+
+
+def sens_apply(params, gain, u0, dstate, dcoeffs=None, params_rows=None, base: str = "plugin", **ipopt) -> np.ndarray:
+    """The correction rule on the host (mpcg_sens_apply): u [B, 2] = clip(u0 + gain [dstate;
+    dcoeffs]) to the handle's (or the row's) ANGVEL and MAXTHR; a NaN gain gives u0."""
+    p = params if isinstance(params, _lib.MpcgParams) else _params_struct(params, "fp64", ipopt, base)
+    dp = C.POINTER(C.c_double)
+    gain, u0, dstate = (np.ascontiguousarray(a, dtype=np.float64) for a in (gain, u0, dstate))
+    B = u0.shape[0]
+    assert gain.shape == (B, 2, _lib.SENS_COLS) and u0.shape == (B, 2) and dstate.shape == (B, 6)
+    dc = rows = None
+    if dcoeffs is not None:
+        dc = np.ascontiguousarray(dcoeffs, dtype=np.float64)
+        assert dc.shape == (B, 4)
+    if params_rows is not None:
+        rows = np.ascontiguousarray(params_rows, dtype=np.float64)
+        assert rows.shape == (B, _lib.PP_FIELDS), "params_rows [B,16]"
+    u = np.zeros((B, 2))
+    _lib.check(_lib.lib().mpcg_sens_apply(C.byref(p), B, rows.ctypes.data_as(dp) if rows is not None else None,
+                                          gain.ctypes.data_as(dp), u0.ctypes.data_as(dp), dstate.ctypes.data_as(dp),
+                                          dc.ctypes.data_as(dp) if dc is not None else None, u.ctypes.data_as(dp)),
+               "mpcg_sens_apply")
+    return u
+
+
 def _on_device(t, shape, dtype="float64"):
     """t is a contiguous torch tensor of this dtype and shape on a GPU."""
     import torch
@@ -186,11 +236,15 @@ class BatchSolver:
 
     # ----------------------------------------------------------------- solve
     def solve(self, state: np.ndarray, coeffs: np.ndarray, want_traj: bool = True, params_rows=None,
-              want_solution: bool = False) -> dict:
+              want_solution: bool = False, want_gain: bool = False) -> dict:
         """params_rows [B, 16] (params.rows): a parameter row per problem instead of the handle's
         per-problem fields (mpcg_solve_pp); a row outside the parameters' domains raises.
         want_solution: also the full solution (mpcg_solve_sol) -- "sol" [B, solution_elems(N)] and
-        its views "x", "zl", "zu" [B, 8N-2] and "lam" [B, 6N] (split_solution)."""
+        its views "x", "zl", "zu" [B, 8N-2] and "lam" [B, 6N] (split_solution).
+        want_gain (with want_solution): also the feedback gains of the records (mpcg_sens) -- "gain"
+        [B, 2, 10] and "sens_info" [B]."""
+        if want_gain and not want_solution:
+            raise ValueError("want_gain needs want_solution: the gain is computed from the record")
         B, out, ptrs = _host_batch(state, coeffs, self.N, want_traj, diag=True)
         rows = None
         if params_rows is not None:
@@ -204,6 +258,9 @@ class BatchSolver:
                                                  sol.ctypes.data_as(dp)), "mpcg_solve_sol")
             out["sol"] = sol
             out.update(split_solution(sol, self.N))
+            if want_gain:
+                g = sens(self.params, state, coeffs, sol, params_rows=rows)
+                out["gain"], out["sens_info"] = g["gain"], g["info"]
             return out
         if params_rows is not None:
             _lib.check(_lib.lib().mpcg_solve_pp(self._h, B, ptrs[0], ptrs[1], rows.ctypes.data_as(C.POINTER(C.c_double)),
@@ -262,6 +319,40 @@ class BatchSolver:
             _on_device(pparams, (B, _lib.PP_FIELDS))
         _lib.check(_lib.lib().mpcg_kkt_device(self._h, B, _ptr(state), _ptr(coeffs), _ptr(pparams), _ptr(sol),
                                               _ptr(cert), _stream_ptr(stream, state)), "mpcg_kkt_device")
+
+    def sens_device(self, state, coeffs, sol, gain, dx=None, info=None, pparams=None, stream=None):
+        """The feedback gains of the records sol [B, solution_elems(N)] on the device
+        (mpcg_sens_device): gain [B, 2, 10] float64, dx [B, 10, 8N-2] float64 and info [B] int32
+        (both optional); the handle's parameters, or a row per problem (pparams [B, 16]).  Queued on
+        the stream, no allocation."""
+        B = state.shape[0]
+        for t, shape in ((state, (B, 6)), (coeffs, (B, 4)), (sol, (B, solution_elems(self.N))),
+                         (gain, (B, 2, _lib.SENS_COLS))):
+            _on_device(t, shape)
+        if dx is not None:
+            _on_device(dx, (B, _lib.SENS_COLS, 8 * self.N - 2))
+        if info is not None:
+            _on_device(info, (B,), "int32")
+        if pparams is not None:
+            _on_device(pparams, (B, _lib.PP_FIELDS))
+        _lib.check(_lib.lib().mpcg_sens_device(self._h, B, _ptr(state), _ptr(coeffs), _ptr(pparams), _ptr(sol),
+                                               _ptr(gain), _ptr(dx), _ptr(info), _stream_ptr(stream, state)),
+                   "mpcg_sens_device")
+
+    def sens_apply_device(self, gain, u0, dstate, u, dcoeffs=None, pparams=None, stream=None):
+        """u [B, 2] = clip(u0 + gain [dstate; dcoeffs]) on the device (mpcg_sens_apply_device), one
+        robot per lane: the correction of a delay-mode prediction without a solve.  dcoeffs [B, 4]
+        or None (0); the limits are the handle's, or the row's (pparams [B, 16])."""
+        B = u0.shape[0]
+        for t, shape in ((gain, (B, 2, _lib.SENS_COLS)), (u0, (B, 2)), (dstate, (B, 6)), (u, (B, 2))):
+            _on_device(t, shape)
+        if dcoeffs is not None:
+            _on_device(dcoeffs, (B, 4))
+        if pparams is not None:
+            _on_device(pparams, (B, _lib.PP_FIELDS))
+        _lib.check(_lib.lib().mpcg_sens_apply_device(self._h, B, _ptr(pparams), _ptr(gain), _ptr(u0), _ptr(dstate),
+                                                     _ptr(dcoeffs), _ptr(u), _stream_ptr(stream, u0)),
+                   "mpcg_sens_apply_device")
 
     # ------------------------------------------------ the benchmark's synthetic robots
     def synth_infinity_device(self, start: int, B: int, M: int = 11, seed: int | None = None, stream=None):
