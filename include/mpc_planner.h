@@ -66,6 +66,22 @@ class MPC {
     // Solve.  gain_info(): mpcg_sens's flag (0 valid; 1, 2: the gain is NaN), -1 before such a Solve.
     const vector<double>& feedback_gain() const { return _gain; }
     int gain_info() const { return _gain_info; }
+    // Start point in (include/mpcg.h mpcg_solve_start): with a mode other than MPCG_START_COLD a
+    // Solve keeps its solution record and the next Solve starts from it as it is -- in the vehicle
+    // frame consecutive ticks solve almost the same problem, and the unshifted record is the
+    // natural start.  MPCG_START_PRIMAL takes the record's x; MPCG_START_FULL takes x and the
+    // multipliers, with the barrier parameter mu0 (the final mu of a converged solve, ~1e-9, leaves
+    // the line search no room; 1e-4 is a default in the range Ipopt users set mu_init to for warm
+    // starts, not a tuned value).  The default mode is MPCG_START_COLD: a default Solve is unchanged
+    // and copies nothing more.  A Solve runs cold while there is no record or STEPS has changed, and
+    // after a Solve whose status is neither 1 (success) nor 4 (acceptable point).
+    // last_start_used(): the mode the last Solve ran in (mpcg_solve_start's start_used).
+    void start_from_solution(int mode, double mu0 = 1e-4) {
+        _start_mode = mode;
+        _start_mu0 = mu0;
+        if (mode == MPCG_START_COLD) _start_rec.clear();
+    }
+    int last_start_used() const { return _start_used; }
     // GPU the solver runs on (default 0); call before the first Solve.
     void set_device(int device) { _device = device; }
 
@@ -87,6 +103,9 @@ class MPC {
     vector<double> _solution;
     vector<double> _gain;
     int _gain_info = -1;
+    int _start_mode = MPCG_START_COLD, _start_used = MPCG_START_COLD;
+    double _start_mu0 = 1e-4;
+    vector<double> _start_rec;  // the last Solve's record while start_from_solution is on
 };
 
 #endif /* MPCG_MPC_PLANNER_H */

@@ -497,6 +497,50 @@ int mpcg_solve_sol(mpcg_handle* h, int64_t B, const double* state, const double*
 int mpcg_solve_device_sol(mpcg_handle* h, int64_t B, const double* d_state, const double* d_coeffs,
                           const double* d_pparams, double* d_u0, double* d_traj, int32_t* d_status, double* d_obj,
                           int32_t* d_iters, int32_t* d_diag, double* d_sol, void* stream);
+/* ---- Start point in ----
+ * The solve of mpcg_solve_sol / mpcg_solve_device_sol started from a solution record per problem:
+ * start [B][mpcg_solution_elems(N)] in the layout above (required), start_mode [B] (required), one
+ * of
+ *   MPCG_START_COLD    the solve of mpcg_solve_device_sol: same iterates, bitwise outputs; the
+ *                      record is not read.
+ *   MPCG_START_PRIMAL  what the reference computes when the record's x is passed as
+ *                      CppAD::ipopt::solve's xi.  Only x is read.  The objective scale and the row
+ *                      scales come from the gradient and the Jacobian at x as given; x is then
+ *                      pushed inside the relaxed bounds (bound_push = bound_frac = 0.01); z = 1,
+ *                      least-squares lambda, mu_init.
+ *   MPCG_START_FULL    Ipopt's warm_start_init_point yes with its 3.12 defaults: the cold solve's
+ *                      scaling; x pushed inside the relaxed bounds by warm_start_bound_push =
+ *                      warm_start_bound_frac = 1e-3; zl, zu from the record, floored at
+ *                      warm_start_mult_bound_push = 1e-3; lambda from the record, 0 where it
+ *                      exceeds warm_start_mult_init_max = 1e6 in magnitude; the barrier parameter
+ *                      mu0[b] (mu0 NULL: the handle's mu_init; read in this mode only); a fresh
+ *                      filter and line search, the iteration count from 0.
+ * start_used [B] (may be NULL) receives the mode that ran: 0, 1 or 2; -1 when the start has a
+ * non-finite entry in a part the mode reads, a negative zl / zu or a mu0 that is not positive and
+ * finite (FULL), or the mode is none of the three; -2 (PRIMAL) when a Jacobian entry at x exceeds
+ * 100 (a row scale other than 1).  A negative value means the problem was solved cold, bitwise the
+ * cold result; nothing traps on a caller's start.  A problem whose parameter row is invalid
+ * (status 13) reports 0.
+ * sol may be NULL, and sol may alias start (the in-place loop): a problem's start is read before
+ * anything of its record is written, by whichever kernel ends up solving it.
+ * The device call is queued on `stream` like mpcg_solve_device_sol: it does not synchronise, does
+ * not allocate after mpcg_reserve, and can be captured in a HIP graph.  d_start, d_start_mode and
+ * d_mu0 are read again for a park-overflow re-solve: keep them unchanged until the stream has
+ * passed the solve, as d_pparams (d_sol aliasing d_start is the exception the solver orders
+ * itself).  Results do not depend on the park capacity or the solve order.
+ * Refused (-1) before anything is launched: a NULL start or start_mode; precision 1.
+ * mpcg_last_kernel reports the k_start_wide instance.  mpcg_multi_*, the ticks and the rollout
+ * are unchanged. */
+#define MPCG_START_COLD 0
+#define MPCG_START_PRIMAL 1
+#define MPCG_START_FULL 2
+int mpcg_solve_start(mpcg_handle* h, int64_t B, const double* state, const double* coeffs, const double* pparams,
+                     const double* start, const int32_t* start_mode, const double* mu0, double* u0, double* traj,
+                     int32_t* status, double* obj, int32_t* iters, int32_t* diag, double* sol, int32_t* start_used);
+int mpcg_solve_device_start(mpcg_handle* h, int64_t B, const double* d_state, const double* d_coeffs,
+                            const double* d_pparams, const double* d_start, const int32_t* d_start_mode,
+                            const double* d_mu0, double* d_u0, double* d_traj, int32_t* d_status, double* d_obj,
+                            int32_t* d_iters, int32_t* d_diag, double* d_sol, int32_t* d_start_used, void* stream);
 /* The KKT certificate of B records, from the NLP alone (the reference's FG_eval and MPC::Solve's
  * original, unrelaxed bounds; no solver code, no scaling): cert [B][4], all unscaled,
  *   0  || grad f + J^T lambda - zl + zu ||_inf

@@ -95,6 +95,9 @@ SIGNATURES = {
     "mpcg_solve_sol": ([C.c_void_p, C.c_int64, _dp, _dp, _dp, _dp, _dp, _ip, _dp, _ip, _ip, _dp], C.c_int),
     "mpcg_solve_device_sol": ([C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p], C.c_int),
+    "mpcg_solve_start": ([C.c_void_p, C.c_int64, _dp, _dp, _dp, _dp, _ip, _dp, _dp, _dp, _ip, _dp, _ip, _ip, _dp, _ip],
+                         C.c_int),
+    "mpcg_solve_device_start": ([C.c_void_p, C.c_int64] + [C.c_void_p] * 15, C.c_int),
     "mpcg_kkt": ([_PP, C.c_int64, _dp, _dp, _dp, _dp, _dp], C.c_int),
     "mpcg_kkt_device": ([C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                          C.c_void_p], C.c_int),
@@ -137,6 +140,7 @@ SIGNATURES = {
                                     C.c_void_p, C.c_void_p], C.c_int),
 }
 
+START_COLD, START_PRIMAL, START_FULL = 0, 1, 2  # MPCG_START_*
 SENS_COLS = 10  # MPCG_SENS_COLS: columns of a gain (6 state components, 4 coefficients)
 PP_FIELDS = 16  # MPCG_PP_FIELDS: doubles per parameter row (their order: params.ROW_KEYS)
 

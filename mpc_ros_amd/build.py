@@ -16,7 +16,7 @@ SOURCES = [os.path.join(CSRC, f) for f in ("mpcg_wide.hip", "mpcg_wide_inst.hip"
                                            "mpcg_kkt.hip", "mpcg_sens.hip",
                                            "mpcg_api.cpp", "mpcg_multi.cpp", "mpc_planner.cpp")]
 INST = os.path.join(CSRC, "mpcg_wide_inst.hip")
-N_INST = 20  # MPCG_INST groups of mpcg_wide_inst.hip (the instance lists of wide_plan.h)
+N_INST = 34  # MPCG_INST groups of mpcg_wide_inst.hip (the instance lists of wide_plan.h)
 HEADERS = [os.path.join(CSRC, f) for f in ("ipm_core.h", "wide_core.h", "wide_plan.h", "wave_dev.h", "mpcg_internal.h",
                                            "mpcg_wide_kern.h", "mpcg_pp.h", "mpcg_window.h", "mpcg_kkt.h", "mpcg_sens.h")] + [
     os.path.join(ROOT, "include", f) for f in ("mpcg.h", "mpc_planner.h")]
@@ -119,7 +119,7 @@ def build(force: bool = False, verbose: bool = False, jobs: int | None = None) -
     if verbose:
         sys.stderr.write(remarks)
     usage = kernel_resources(remarks)
-    bad = [k for k, u in usage.items() if ("k_solve_wide" in k or "k_resume_wide" in k) and u.get("LDS Size [bytes/block]", 0) != 0]
+    bad = [k for k, u in usage.items() if ("k_solve_wide" in k or "k_resume_wide" in k or "k_start_wide" in k) and u.get("LDS Size [bytes/block]", 0) != 0]
     if bad:
         os.remove(LIB + ".tmp")
         raise RuntimeError(f"static LDS in {bad}: the solver addresses its dynamic LDS from 0")
@@ -144,7 +144,7 @@ def save_resources(usage: dict, path: str = RESOURCES) -> None:
     restoration phase's out-of-line function, from the build's kernel-resource-usage remarks."""
     import json
 
-    keep = {k: v for k, v in usage.items() if "k_solve_wide" in k or "k_resume_wide" in k or "resto_phase" in k}
+    keep = {k: v for k, v in usage.items() if "k_solve_wide" in k or "k_resume_wide" in k or "k_start_wide" in k or "resto_phase" in k}
     names = demangle(sorted(keep))
     os.makedirs(os.path.dirname(path), exist_ok=True)
     with open(path, "w") as f:

@@ -39,7 +39,8 @@ MPC::MPC(const MPC& o)
       _etheta_start(o._etheta_start), _angvel_start(o._angvel_start), _a_start(o._a_start), _params(o._params),
       _device(o._device), _handle(nullptr), _last_status(o._last_status), _last_iters(o._last_iters),
       _last_obj(o._last_obj), _keep_solution(o._keep_solution), _solution(o._solution),
-      _gain(o._gain), _gain_info(o._gain_info) {}
+      _gain(o._gain), _gain_info(o._gain_info), _start_mode(o._start_mode), _start_used(o._start_used),
+      _start_mu0(o._start_mu0), _start_rec(o._start_rec) {}
 
 MPC& MPC::operator=(const MPC& o) {
     if (this == &o) return *this;
@@ -68,6 +69,10 @@ MPC& MPC::operator=(const MPC& o) {
     _solution = o._solution;
     _gain = o._gain;
     _gain_info = o._gain_info;
+    _start_mode = o._start_mode;
+    _start_used = o._start_used;
+    _start_mu0 = o._start_mu0;
+    _start_rec = o._start_rec;
     return *this;  // keeps its own GPU handle
 }
 
@@ -131,7 +136,19 @@ vector<double> MPC::SolveRaw(const double* state, const double* coeffs) {
     double u0[2] = {0, 0}, obj = 0;
     int32_t status = 0, iters = 0;
     int rc;
-    if (_keep_solution) {
+    if (_start_mode != MPCG_START_COLD) {
+        // from the last Solve's record, in place (cold while there is none for this horizon)
+        const size_t ne = (size_t)mpcg_solution_elems(N);
+        int32_t mode = _start_rec.size() == ne ? _start_mode : MPCG_START_COLD, used = 0;
+        if (_start_rec.size() != ne) _start_rec.assign(ne, 0.0);
+        rc = mpcg_solve_start(_handle, 1, state, coeffs, nullptr, _start_rec.data(), &mode, &_start_mu0, u0,
+                              traj.data(), &status, &obj, &iters, nullptr, _start_rec.data(), &used);
+        if (_keep_solution) _solution = _start_rec;
+        // (a failed call or a solve that ended neither at a solution nor at an acceptable point
+        // leaves no record: the next Solve starts cold)
+        _start_used = rc ? MPCG_START_COLD : used;
+        if (rc || !(status == 1 || status == 4)) _start_rec.clear();
+    } else if (_keep_solution) {
         _solution.assign((size_t)mpcg_solution_elems(N), 0.0);
         rc = mpcg_solve_sol(_handle, 1, state, coeffs, nullptr, u0, traj.data(), &status, &obj, &iters, nullptr,
                             _solution.data());
@@ -146,6 +163,7 @@ vector<double> MPC::SolveRaw(const double* state, const double* coeffs) {
     _last_status = status;
     _last_iters = iters;
     _last_obj = obj;
+    if (_start_mode == MPCG_START_COLD) _start_used = MPCG_START_COLD;
     if (_keep_solution) {
         // (one record: the sweeps on the host, a few microseconds at N = 20)
         const mpcg_params p = effective_params();

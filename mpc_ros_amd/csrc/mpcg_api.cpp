@@ -450,7 +450,8 @@ static int lds_refusal(const mpcg_handle* h) {
 // the refusals, grown the solver's scratch (ensure_solve) and ordered s (with_scratch).
 static int queue_solve(mpcg_handle* h, int64_t B, const double* d_state, const double* d_coeffs,
                        const double* d_pparams, double* d_u0, double* d_traj, int32_t* d_status, double* d_obj,
-                       int32_t* d_iters, int32_t* d_diag, hipStream_t s, double* d_sol = nullptr) {
+                       int32_t* d_iters, int32_t* d_diag, hipStream_t s, double* d_sol = nullptr,
+                       const mpcg::WideStart* start = nullptr) {
     // batches larger than the resident wavefronts (8 per CU) are solved in
     // expected-longest-first order (launch_wide_order)
     int32_t* order = nullptr;
@@ -466,7 +467,7 @@ static int queue_solve(mpcg_handle* h, int64_t B, const double* d_state, const d
     ws.ev_join2 = h->ev_join2;
     hipError_t e = mpcg::launch_wide_solve(handle_ipm(h), B, d_state, d_coeffs, d_u0, d_traj, d_status, d_obj, d_iters,
                                            d_diag, order, h->d_spill.p, h->d_spill.bytes, s, ws, &h->last_kernel,
-                                           d_pparams, d_sol);
+                                           d_pparams, d_sol, start);
     if (e != hipSuccess) return hip_fail(e, "wide solve launch");
     h->last_ordered = order != nullptr;
     return 0;
@@ -519,6 +520,107 @@ int mpcg_solve_device_sol(mpcg_handle* h, int64_t B, const double* d_state, cons
                           int32_t* d_iters, int32_t* d_diag, double* d_sol, void* stream) {
     return solve_device(h, B, d_state, d_coeffs, d_pparams, d_u0, d_traj, d_status, d_obj, d_iters, d_diag, stream,
                         d_sol, true);
+}
+
+// ---- start point in ----
+static const char kNoFp32Start[] = "precision 1 (fp32) takes no start point: the started solve has fp64 instances only";
+
+int mpcg_solve_device_start(mpcg_handle* h, int64_t B, const double* d_state, const double* d_coeffs,
+                            const double* d_pparams, const double* d_start, const int32_t* d_start_mode,
+                            const double* d_mu0, double* d_u0, double* d_traj, int32_t* d_status, double* d_obj,
+                            int32_t* d_iters, int32_t* d_diag, double* d_sol, int32_t* d_start_used, void* stream) {
+    // (the start first: an argument check that needs no handle)
+    if (!d_start || !d_start_mode) return fail(-1, "start and start_mode are required");
+    int rc = batch_check(h, B);
+    if (rc) return rc;
+    if (h->params.precision != 0) return fail(-1, kNoFp32Start);
+    if (B == 0) return 0;
+    if (!d_state || !d_coeffs || !d_u0) return fail(-1, "state, coeffs and u0 are required");
+    rc = params_refusal(h, d_pparams != nullptr);
+    if (rc) return rc;
+    hipError_t e = hipSetDevice(h->device);
+    if (e != hipSuccess) return hip_fail(e, "hipSetDevice");
+    hipStream_t s = (hipStream_t)stream;
+    rc = lds_refusal(h);
+    if (rc == 0) rc = ensure_solve(h, B);
+    if (rc) return rc;
+    const mpcg::WideStart st{d_start, d_start_mode, d_mu0, d_start_used};
+    return with_scratch(h, s, [&] {
+        return queue_solve(h, B, d_state, d_coeffs, d_pparams, d_u0, d_traj, d_status, d_obj, d_iters, d_diag, s,
+                           d_sol, &st);
+    });
+}
+
+int mpcg_solve_start(mpcg_handle* h, int64_t B, const double* state, const double* coeffs, const double* pparams,
+                     const double* start, const int32_t* start_mode, const double* mu0, double* u0, double* traj,
+                     int32_t* status, double* obj, int32_t* iters, int32_t* diag, double* sol, int32_t* start_used) {
+    if (!start || !start_mode) return fail(-1, "start and start_mode are required");
+    int rc = batch_check(h, B);
+    if (rc) return rc;
+    if (h->params.precision != 0) return fail(-1, kNoFp32Start);
+    if (B == 0) return 0;
+    if (!state || !coeffs || !u0) return fail(-1, "state, coeffs and u0 are required");
+    rc = mpcg_params_check(&h->params);
+    if (rc) return rc;
+    if (pparams) {
+        rc = mpcg_pparams_check(pparams, B, h->params.model, nullptr);
+        if (rc) return rc;
+    }
+    const int N = h->params.steps;
+    // io block (doubles): state 6 | coeffs 4 | u0 2 | traj 3N | obj 1 | mu0 1 | the records (start
+    // in, the solution out in place) | the parameter rows 16 | then int32: status, iters, mode,
+    // used, diag 4
+    const size_t ne = (size_t)mpcg::solution_elems(N), nb = (size_t)B;
+    const size_t nd = (size_t)(6 + 4 + 2 + 3 * N + 1 + 1) + ne + (pparams ? MPCG_PP_FIELDS : 0);
+    const size_t need = (nd * sizeof(double) + 8 * sizeof(int32_t)) * nb;
+    hipError_t e = hipSetDevice(h->device);
+    if (e != hipSuccess) return hip_fail(e, "hipSetDevice");
+    rc = ensure(h, h->d_io, need, "hipMalloc(io)");
+    if (rc) return rc;
+    double* ds = (double*)h->d_io.p;
+    double* dc = ds + 6 * nb;
+    double* du = dc + 4 * nb;
+    double* dt = du + 2 * nb;
+    double* dob = dt + (size_t)3 * N * nb;
+    double* dmu = dob + nb;
+    double* drec = dmu + nb;
+    double* dpp = drec + ne * nb;
+    int32_t* dst = (int32_t*)(dpp + (pparams ? (size_t)MPCG_PP_FIELDS * nb : 0));
+    int32_t* dit = dst + nb;
+    int32_t* dmd = dit + nb;
+    int32_t* dus = dmd + nb;
+    int32_t* ddg = dus + nb;
+    e = hipMemcpyAsync(ds, state, sizeof(double) * 6 * nb, hipMemcpyHostToDevice, h->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(dc, coeffs, sizeof(double) * 4 * nb, hipMemcpyHostToDevice, h->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(drec, start, sizeof(double) * ne * nb, hipMemcpyHostToDevice, h->stream);
+    if (e == hipSuccess)
+        e = hipMemcpyAsync(dmd, start_mode, sizeof(int32_t) * nb, hipMemcpyHostToDevice, h->stream);
+    if (e == hipSuccess && mu0) e = hipMemcpyAsync(dmu, mu0, sizeof(double) * nb, hipMemcpyHostToDevice, h->stream);
+    if (e == hipSuccess && pparams)
+        e = hipMemcpyAsync(dpp, pparams, sizeof(double) * MPCG_PP_FIELDS * nb, hipMemcpyHostToDevice, h->stream);
+    if (e != hipSuccess) return hip_fail(e, "hipMemcpy H2D");
+    // (the records are solved in place on the device: sol aliases start there)
+    rc = mpcg_solve_device_start(h, B, ds, dc, pparams ? dpp : nullptr, drec, dmd, mu0 ? dmu : nullptr, du, dt, dst,
+                                 dob, dit, diag ? ddg : nullptr, sol ? drec : nullptr, dus, h->stream);
+    if (rc) return rc;
+    e = hipMemcpyAsync(u0, du, sizeof(double) * 2 * nb, hipMemcpyDeviceToHost, h->stream);
+    if (e == hipSuccess && traj)
+        e = hipMemcpyAsync(traj, dt, sizeof(double) * 3 * N * nb, hipMemcpyDeviceToHost, h->stream);
+    if (e == hipSuccess && obj) e = hipMemcpyAsync(obj, dob, sizeof(double) * nb, hipMemcpyDeviceToHost, h->stream);
+    if (e == hipSuccess && status)
+        e = hipMemcpyAsync(status, dst, sizeof(int32_t) * nb, hipMemcpyDeviceToHost, h->stream);
+    if (e == hipSuccess && iters)
+        e = hipMemcpyAsync(iters, dit, sizeof(int32_t) * nb, hipMemcpyDeviceToHost, h->stream);
+    if (e == hipSuccess && diag)
+        e = hipMemcpyAsync(diag, ddg, sizeof(int32_t) * 4 * nb, hipMemcpyDeviceToHost, h->stream);
+    if (e == hipSuccess && start_used)
+        e = hipMemcpyAsync(start_used, dus, sizeof(int32_t) * nb, hipMemcpyDeviceToHost, h->stream);
+    if (e == hipSuccess && sol)
+        e = hipMemcpyAsync(sol, drec, sizeof(double) * ne * nb, hipMemcpyDeviceToHost, h->stream);
+    if (e != hipSuccess) return hip_fail(e, "hipMemcpy D2H");
+    e = hipStreamSynchronize(h->stream);
+    if (e != hipSuccess) return hip_fail(e, "hipStreamSynchronize");
+    return 0;
 }
 
 int64_t mpcg_solution_elems(int32_t N) { return N >= 2 ? mpcg::solution_elems(N) : 0; }

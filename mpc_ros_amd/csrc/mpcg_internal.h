@@ -30,11 +30,21 @@ struct WideStreams {
     hipStream_t aux = nullptr, aux2 = nullptr;
     hipEvent_t ev_fork = nullptr, ev_join = nullptr, ev_join2 = nullptr;
 };
+// A started solve (mpcg_solve_device_start): the start records [B][solution_elems(N)], the mode
+// of each problem, the barrier parameter of each FULL start (or null: mu_init) and the mode that
+// ran (or null), all on the device -- the k_start_wide / k_resume_wide_start instances; fp64 only
+struct WideStart {
+    const double* rec = nullptr;
+    const int32_t* mode = nullptr;
+    const double* mu0 = nullptr;
+    int32_t* used = nullptr;
+};
 hipError_t launch_wide_solve(const IpmParams& P, int64_t B, const double* state, const double* coeffs, double* u0,
                              double* traj, int32_t* status, double* obj, int32_t* iters, int32_t* diag,
                              const int32_t* order, void* spill, size_t spill_bytes, hipStream_t stream,
                              const WideStreams& ws = WideStreams(), const char** kernel_name = nullptr,
-                             const double* pparams = nullptr, double* sol = nullptr);
+                             const double* pparams = nullptr, double* sol = nullptr,
+                             const WideStart* start = nullptr);
 // (pparams: a parameter row per problem, [B][16] doubles in include/mpcg.h's MPCG_PP_* order,
 // on the device -- the k_solve_wide_pp / k_resume_wide_pp instances; fp64 only)
 // (sol: the solution records [B][solution_elems(N)] on the device, written by every ending's

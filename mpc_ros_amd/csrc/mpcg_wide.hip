@@ -69,7 +69,7 @@ constexpr bool kHeadlineOnly = true;
 #else
 constexpr bool kHeadlineOnly = false;
 #endif
-enum InstKind { SOLVE, WARM, RESUME, PP_SOLVE, PP_RESUME };
+enum InstKind { SOLVE, WARM, RESUME, PP_SOLVE, PP_RESUME, START_SOLVE, START_RESUME };
 template <int KIND, int M, bool S, class T, int NB, bool D, int W>
 static const void* inst_fn() {
     if constexpr (kHeadlineOnly && !((KIND == SOLVE || KIND == RESUME) && M == 0 && S && sizeof(T) == 8 && NB == 1 && D))
@@ -82,6 +82,10 @@ static const void* inst_fn() {
         return pp_solve_kernel_fn<M, S, T, NB, D, W>();
     else if constexpr (KIND == PP_RESUME)
         return pp_resume_kernel_fn<M, S, T, NB>();
+    else if constexpr (KIND == START_SOLVE)
+        return start_kernel_fn<M, S, T, NB, D, W>();
+    else if constexpr (KIND == START_RESUME)
+        return start_resume_kernel_fn<M, S, T, NB>();
     else
         return resume_kernel_fn<M, S, T, NB>();
 }
@@ -98,6 +102,12 @@ static const WideInst kResumeInst[] = {MPCG_WIDE_RESUME_INSTANCES(MPCG_ENT_RESUM
 #define MPCG_ENT_PP_RESUME(g, M, S, T, NB) {inst_fn<PP_RESUME, M, S, T, NB, true, 0>(), MPCG_PP_RESUME_NAME(M, S, T, NB)},
 static const WideInst kPPSolveInst[] = {MPCG_WIDE_PP_SOLVE_INSTANCES(MPCG_ENT_PP_SOLVE)};
 static const WideInst kPPResumeInst[] = {MPCG_WIDE_PP_RESUME_INSTANCES(MPCG_ENT_PP_RESUME)};
+// (the started solve's instances: kStartKeys / kStartResumeKeys)
+#define MPCG_ENT_START(g, M, S, T, NB, D, W) {inst_fn<START_SOLVE, M, S, T, NB, D, W>(), MPCG_START_NAME(M, S, T, NB, D, W)},
+#define MPCG_ENT_START_RESUME(g, M, S, T, NB) \
+    {inst_fn<START_RESUME, M, S, T, NB, true, 0>(), MPCG_START_RESUME_NAME(M, S, T, NB)},
+static const WideInst kStartInst[] = {MPCG_WIDE_START_INSTANCES(MPCG_ENT_START)};
+static const WideInst kStartResumeInst[] = {MPCG_WIDE_START_RESUME_INSTANCES(MPCG_ENT_START_RESUME)};
 // the instance of a key; fn null: the key is none (refused parameters) or not in the library
 template <size_t n>
 static WideInst find_inst(const WideKey (&keys)[n], const WideInst (&inst)[n], const WideKey& k) {
@@ -109,6 +119,7 @@ WideInst wide_kernel(const IpmParams& P, int64_t B) { return find_inst(kSolveKey
 WideInst wide_pp_kernel(const IpmParams& P, int64_t B) {
     return find_inst(kPPSolveKeys, kPPSolveInst, pp_solve_key(P, B));
 }
+WideInst wide_start_kernel(const IpmParams& P) { return find_inst(kStartKeys, kStartInst, start_key(P)); }
 
 // XCDs of the current device (HW_REG_XCC_ID partitions of the workspace slots); 8 on an
 // MI355X in SPX mode, fewer on a partitioned device
@@ -212,6 +223,9 @@ struct PhaseLaunch {
     // per-problem parameter rows [n_prob][16] (inst: a k_solve_wide_pp instance; the resume
     // launches then take the k_resume_wide_pp instance and the same rows), or null
     const double* pparams = nullptr;
+    // a started solve (inst: a k_start_wide instance; the resume launches take the
+    // k_resume_wide_start instance and the same argument, which carries the rows), or null
+    const StartIn* start = nullptr;
 };
 // the solver addresses its dynamic LDS from address 0 (wave_dev.h): no static LDS
 static hipError_t set_dynamic_lds(const void* fn, size_t lds) {
@@ -239,6 +253,7 @@ static hipError_t launch_phase(const WideProblem& pb, const PhaseLaunch& L, bool
     if (!fn) return hipErrorInvalidValue;
     const bool fp32_phase = P.precision == 1 && L.handoff;  // (parks nothing: its endings go to the hand-over)
     const void* rf = fp32_phase  ? nullptr
+                     : L.start   ? find_inst(kStartResumeKeys, kStartResumeInst, start_resume_key(P)).fn
                      : L.pparams ? find_inst(kPPResumeKeys, kPPResumeInst, pp_resume_key(P)).fn
                                  : find_inst(kResumeKeys, kResumeInst, resume_key(P)).fn;
     if (!fp32_phase && !rf) return hipErrorInvalidValue;
@@ -262,8 +277,10 @@ static hipError_t launch_phase(const WideProblem& pb, const PhaseLaunch& L, bool
                .handoff_stride = L.handoff ? L.handoff_stride : 0, .sol = pb.sol,
                .sol_stride = solution_elems(P.N)};
     // (the per-problem kernels take the rows as a second argument, after WideArgs)
+    // (the started solve's kernels take StartIn there instead)
     const double* rows = L.pparams;
-    void* args[] = {(void*)&a, (void*)&rows};
+    void* second = L.start ? (void*)L.start : (void*)&rows;
+    void* args[] = {(void*)&a, second};
     // the resume workers: parked problems (the restoration phase) continued by k_resume_wide
     // fork: the resume workers on the aux stream alongside the batch kernel (the fork point is
     // before the batch kernel); join: the stream continues after both (no host
@@ -318,7 +335,7 @@ static hipError_t launch_phase(const WideProblem& pb, const PhaseLaunch& L, bool
     if (W.has_ovf()) {
         WideArgs ao = a;
         ao.phase = 1;
-        void* oargs[] = {(void*)&ao, (void*)&rows};
+        void* oargs[] = {(void*)&ao, second};
         e = hipLaunchKernel(rf, dim3((unsigned)pc), dim3(64), oargs, lds, L.stream);
         if (e != hipSuccess) return e;
     }
@@ -329,7 +346,7 @@ hipError_t launch_wide_solve(const IpmParams& P, int64_t B, const double* state,
                              double* traj, int32_t* status, double* obj, int32_t* iters, int32_t* diag,
                              const int32_t* order, void* spill, size_t spill_bytes, hipStream_t stream,
                              const WideStreams& ws, const char** kernel_name, const double* pparams,
-                             double* sol) {
+                             double* sol, const WideStart* start) {
     if (B <= 0) return hipSuccess;
     if (!spill) return hipErrorInvalidValue;
     const SolveLayout W = solve_layout(P, B);
@@ -337,10 +354,20 @@ hipError_t launch_wide_solve(const IpmParams& P, int64_t B, const double* state,
     const WideProblem pb{state, coeffs, u0, traj, status, obj, iters, diag, B, sol};
     // (per-problem rows: the same workspace -- the per-problem instance has its plain twin's LDS
     // size and register allocation, so the slot budget is the plain instance's)
-    PhaseLaunch L{.P = P, .inst = pparams ? wide_pp_kernel(P, B) : wide_kernel(P, B), .B = B, .order = order,
-                  .lay = &W.first, .base = (char*)spill, .stream = stream, .aux = ws.aux, .ev_fork = ws.ev_fork,
-                  .ev_join = ws.ev_join, .pparams = pparams};
+    PhaseLaunch L{.P = P, .inst = start     ? wide_start_kernel(P)
+                                  : pparams ? wide_pp_kernel(P, B)
+                                            : wide_kernel(P, B),
+                  .B = B, .order = order, .lay = &W.first, .base = (char*)spill, .stream = stream, .aux = ws.aux,
+                  .ev_fork = ws.ev_fork, .ev_join = ws.ev_join, .pparams = pparams};
     if (!L.inst.fn) return hipErrorInvalidValue;
+    // (a started solve: the rows travel in StartIn; fp64 only -- start_key)
+    const StartIn si{start ? start->rec : nullptr, solution_elems(P.N), start ? start->mode : nullptr,
+                      start ? start->mu0 : nullptr, start ? start->used : nullptr, pparams};
+    if (start) {
+        if (W.two || !start->rec || !start->mode) return hipErrorInvalidValue;
+        L.start = &si;
+        L.pparams = nullptr;
+    }
     if (pparams && W.two) return hipErrorInvalidValue;  // (the fp32 configuration: refused, wide_plan.h pp_solve_key)
     if (kernel_name) *kernel_name = L.inst.name;
     if (!W.two) return launch_phase(pb, L);

@@ -70,6 +70,19 @@ struct WideArgs {
     double* sol;
     int64_t sol_stride;
 };
+// A solve started from solution records (k_start_wide, k_resume_wide_start; include/mpcg.h
+// mpcg_solve_device_start): the records [n_prob][stride] (WideSolver::solution_out's layout),
+// the mode of each problem, the barrier parameter of each FULL start (or null: mu_init), the
+// mode that ran (or null), and a parameter row per problem (or null: the handle's parameters).
+// All constant for the launch: the overflow re-solve reads them again.
+struct StartIn {
+    const double* start;
+    int64_t stride;
+    const int32_t* mode;
+    const double* mu0;
+    int32_t* used;
+    const double* pparams;
+};
 // Always-on range checks of the indices a kernel reads from device memory (the solve order, the
 // park area's problem indices, the overflow list, a parked entry's counts) or derives from the
 // workspace's counters (slot, park entry): a value out of range is reported and the kernel
@@ -209,8 +222,14 @@ __device__ __forceinline__ void pp_invalid_out(const WideArgs& a, int64_t p) {
 // (include/mpcg.h MPCG_PP_*), N, the model and the options from a.P; the row is loaded once by
 // scalar loads (pp_load_row), moved to VGPRs, checked before the solve (pp_invalid_out: no
 // trap) and applied from the same registers.
-template <int MODEL, bool SPLIT, class T, int NB, bool DEFOPT, bool WARM, bool PP = false, bool RCK = false>
-__device__ __forceinline__ void solve_body(const WideArgs& a, const double* pparams = nullptr) {
+// START (k_start_wide): the problem starts from its solution record in the mode the caller gives
+// it (WideSolver::init_start; the mode is wave-uniform), with a parameter row where the launch
+// has rows (a run-time choice of the one instance: the row stays wave-uniform).  The record is
+// read before the solve, so the record the ending writes may be the same memory.
+template <int MODEL, bool SPLIT, class T, int NB, bool DEFOPT, bool WARM, bool PP = false, bool RCK = false,
+          bool START = false>
+__device__ __forceinline__ void solve_body(const WideArgs& a, const double* pparams = nullptr,
+                                           const StartIn* sa = nullptr) {
     if ((int64_t)blockIdx.x >= a.B) return;
     const int64_t p = a.order ? (int64_t)a.order[blockIdx.x] : (int64_t)blockIdx.x;
     check_index_quiet(p, a.n_prob);
@@ -234,6 +253,18 @@ __device__ __forceinline__ void solve_body(const WideArgs& a, const double* ppar
         }
         pp_row_apply(row.f, Pk);
     }
+    if constexpr (START) {
+        if (sa->pparams) {
+            const PPRow row = pp_load_row(sa->pparams, p);
+            if (!pp_row_ok(row.f, MODEL)) {
+                pp_invalid_out(a, p);
+                if (sa->used && t == 0) sa->used[p] = 0;  // (nothing ran)
+                block_done(a.done);
+                return;
+            }
+            pp_row_apply(row.f, Pk);
+        }
+    }
     const int slot = claim_slot(a.slot_flags, a.nslots, a.nxcc, (int64_t)blockIdx.x);
     check_index_quiet(slot, a.nslots);
     // (RCK: the reciprocal slacks kept in registers -- WideSolver RCK -- in the instance the
@@ -247,6 +278,12 @@ __device__ __forceinline__ void solve_body(const WideArgs& a, const double* ppar
         else
             S.init();
         S.run();  // (one call site of the solver's loop)
+    } else if constexpr (START) {
+        const int md = __builtin_amdgcn_readfirstlane(sa->mode[p]);
+        const double m0 = sa->mu0 ? sa->mu0[p] : Pk.mu_init;
+        const int used = S.init_start(sa->start + p * sa->stride, md, (T)m0);
+        if (sa->used && t == 0) sa->used[p] = used;
+        S.run();
     } else {
         S.solve();
     }
@@ -316,6 +353,13 @@ template <int MODEL, bool SPLIT, class T, int NB, bool DEFOPT = false, int WPE =
 __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE, WPE)))
 k_solve_wide_pp(WideArgs a, const double* pparams) {
     solve_body<MODEL, SPLIT, T, NB, DEFOPT, false, true>(a, pparams);
+}
+
+// the batch kernel of a solve started from solution records (mpcg_solve_device_start)
+template <int MODEL, bool SPLIT, class T, int NB, bool DEFOPT = false, int WPE = 2>
+__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE, WPE)))
+k_start_wide(WideArgs a, StartIn sa) {
+    solve_body<MODEL, SPLIT, T, NB, DEFOPT, false, false, false, true>(a, nullptr, &sa);
 }
 
 // results of problem p (u0, status, iterations, objective, trajectory; honor_original_bounds)
@@ -559,6 +603,63 @@ k_resume_wide_pp(WideArgs a, const double* pparams) {
     }
 }
 
+// k_resume_wide for a started solve (mpcg_solve_device_start; fp64, no hand-over): a parked problem
+// is continued from its park entry, which holds the started solve's iterate, row scales and
+// objective scale; an overflow problem starts again from its record (unchanged: the batch kernel
+// wrote no output of a problem it listed) in its mode, under its parameter row where the launch
+// has rows.  A copy of k_resume_wide_pp's body but for that -- a change to the protocol belongs
+// in all three.
+template <int MODEL, bool SPLIT, class T, int NB>
+__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 1)))
+k_resume_wide_start(WideArgs a, StartIn sa) {
+    const int t = threadIdx.x;
+    const WideLayout Lw(a.P.N, a.P.filter_cap, MODEL);
+    typedef WideSolver<DevWave, MODEL, SPLIT, T, NB, false, false> Solver;  // (RCK: no registers to spare here)
+    for (;;) {
+        int64_t p;
+        T* ent;
+        if (a.phase == 0) {
+            const int e = take_parked(a);
+            if (e < 0) return;
+            check_index("parked entry", e, a.park_cap);
+            p = a.park_idx[e];
+            check_index("parked problem", p, a.n_prob);
+            ent = (T*)a.park + (int64_t)e * a.park_stride;
+        } else {
+            p = take_overflow(a);
+            if (p < 0) return;
+            check_index("overflow problem", p, a.n_prob);
+            check_index("overflow worker's park entry", (int64_t)a.ent0 + blockIdx.x, a.park_cap);
+            ent = (T*)a.park + (int64_t)(a.ent0 + blockIdx.x) * a.park_stride;
+        }
+        IpmProblem<T> pr;
+#pragma unroll
+        for (int j = 0; j < 6; ++j) pr.init[j] = (T)a.state[p * 6 + j];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) pr.c[j] = (T)a.coeffs[p * 4 + j];
+        DevWave wv;
+        wv.t = t;
+        IpmParams Pk = a.P;
+        if (sa.pparams) {
+            const PPRow row = pp_load_row(sa.pparams, p);
+            pp_row_apply(row.f, Pk);
+        }
+        Solver S(Pk, pr, wv, ent + Solver::PARK_SCALARS + Lw.total());
+        if (a.phase == 0) {
+            if (!S.park_entry_ok(ent, p)) index_fault("parked entry's tag / counts: problem", p, a.n_prob);
+            S.unpark(ent);
+        } else {
+            const int md = __builtin_amdgcn_readfirstlane(sa.mode[p]);
+            const double m0 = sa.mu0 ? sa.mu0[p] : Pk.mu_init;
+            const int used = S.init_start(sa.start + p * sa.stride, md, (T)m0);
+            if (sa.used && t == 0) sa.used[p] = used;
+            S.run();
+        }
+        S.finish_resto();
+        write_out(a, S, p, a.phase == 0 ? 1 : a.ovf_mark);
+    }
+}
+
 // Kernel instances (host stubs), defined in mpcg_wide_inst.hip: the instance of
 // k_solve_wide<MODEL, SPLIT, T, NB, DEFOPT, WPE> / k_resume_wide<MODEL, SPLIT, T, NB>.
 template <int MODEL, bool SPLIT, class T, int NB, bool DEFOPT, int WPE>
@@ -580,6 +681,12 @@ const void* pp_solve_kernel_fn();
 template <int MODEL, bool SPLIT, class T, int NB>
 const void* pp_resume_kernel_fn();
 WideInst wide_pp_kernel(const IpmParams& P, int64_t B);
+// (the started solve's instances, k_start_wide / k_resume_wide_start: wide_plan.h start_key / start_resume_key)
+template <int MODEL, bool SPLIT, class T, int NB, bool DEFOPT, int WPE>
+const void* start_kernel_fn();
+template <int MODEL, bool SPLIT, class T, int NB>
+const void* start_resume_kernel_fn();
+WideInst wide_start_kernel(const IpmParams& P);
 
 // (the instances the library carries: the lists of wide_plan.h)
 #define MPCG_DECL_SOLVE(g, M, S, T, NB, D, W) template <> const void* solve_kernel_fn<M, S, T, NB, D, W>();
@@ -592,6 +699,12 @@ MPCG_WIDE_WARM_INSTANCES(MPCG_DECL_WARM)
 #define MPCG_DECL_PP_RESUME(g, M, S, T, NB) template <> const void* pp_resume_kernel_fn<M, S, T, NB>();
 MPCG_WIDE_PP_SOLVE_INSTANCES(MPCG_DECL_PP_SOLVE)
 MPCG_WIDE_PP_RESUME_INSTANCES(MPCG_DECL_PP_RESUME)
+#define MPCG_DECL_START(g, M, S, T, NB, D, W) template <> const void* start_kernel_fn<M, S, T, NB, D, W>();
+#define MPCG_DECL_START_RESUME(g, M, S, T, NB) template <> const void* start_resume_kernel_fn<M, S, T, NB>();
+MPCG_WIDE_START_INSTANCES(MPCG_DECL_START)
+MPCG_WIDE_START_RESUME_INSTANCES(MPCG_DECL_START_RESUME)
+#undef MPCG_DECL_START
+#undef MPCG_DECL_START_RESUME
 #undef MPCG_DECL_PP_SOLVE
 #undef MPCG_DECL_PP_RESUME
 #undef MPCG_DECL_SOLVE

@@ -3932,6 +3932,171 @@ struct WideSolver : RcRegs<TT, wide_fuse_rc<SPLIT, TT, RCK>()> {
         do_stats(false, (T)0, (T)0, K_BEGIN);
     }
 
+    // ------------------------------------------------------------ start point in
+    // A solve started from a caller's solution record (include/mpcg.h MPCG_START_*; the record's
+    // layout and unscaling are solution_out's, read here through the inverse of its index map,
+    // the 64 lanes striding it).
+    //   START_PRIMAL: what the reference computes with the record's x as its xi -- the objective
+    //     and row scaling from the gradient and the Jacobian at the unpushed point
+    //     (scaling_at_point), x pushed inside the relaxed bounds (bound_push = bound_frac =
+    //     0.01), z = 1, least-squares lambda, mu_init.  The row scales of a usable start are all
+    //     1 (the RSC table is written as ones); a start with a Jacobian entry above 100 is not
+    //     used (-2).
+    //   START_FULL: Ipopt's warm_start_init_point with its 3.12 defaults -- the cold solve's
+    //     scaling (setup), x pushed by warm_start_bound_push = _frac = 1e-3, z_L, z_U times sf
+    //     floored at warm_start_mult_bound_push = 1e-3, lambda times sf (0 beyond
+    //     warm_start_mult_init_max = 1e6), the barrier parameter mu0, a fresh filter and
+    //     line-search state, iteration count 0; then the algorithm as from any iterate.
+    // Returns the mode that ran: 0, 1, 2; -1 (a non-finite entry in a part the mode reads, a
+    // negative bound multiplier or a barrier parameter that is not positive and finite in FULL
+    // mode, an unknown mode) and -2 mean the cold start (init()), bitwise.  Wave-uniform; leaves
+    // the first sweep set, as init() / init_warm() do.
+    enum : int { START_COLD = 0, START_PRIMAL = 1, START_FULL = 2 };
+    MPCG_HD T push_k(T v, T lo, T hi, T kp) const {
+        const T pl = tmin(kp * tmax((T)1, (T)fabs(lo)), kp * (hi - lo));
+        const T pu = tmin(kp * tmax((T)1, (T)fabs(hi)), kp * (hi - lo));
+        if (v < lo + pl) v = lo + pl;
+        if (v > hi - pu) v = hi - pu;
+        return v;
+    }
+    // stage k, variable j of entry e of the record's x (and z_L, z_U) part
+    MPCG_HD void rec_var(int e, int* j, int* k) const {
+        const int nc = 6 * N;
+        if (e < nc) {
+            *j = e / N;
+            *k = e - *j * N;
+        } else {
+            *j = 6 + (e - nc) / (N - 1);
+            *k = (e - nc) - (*j - 6) * (N - 1);
+        }
+    }
+    // The largest entries of grad f (*gmax) and of the Jacobian (*jmax; its +-1 entries left
+    // out: only the test against 100 is taken from it) at the point in LDS W, lane k = stage k.
+    MPCG_HD void scaling_at_point(T* gmax, T* jmax) {
+        const int t = wv.lane();
+        T gm = 0, jm = 0;
+        for (int b = 0; b < NB; ++b) {
+            const int k = t + 64 * b;
+            if (k >= N) continue;
+            T w[8], g[6], up[2] = {0, 0}, um[2] = {0, 0};
+            ldn<8>(L.W(k), w);
+            grad_state(w, g);
+            gm = tmax(gm, tmax((T)fabs(g[3]), tmax((T)fabs(g[4]), (T)fabs(g[5]))));
+            if (k < N - 1) {
+                if (k >= 1) {
+                    um[0] = ld(L.W(k - 1) + 6);
+                    um[1] = ld(L.W(k - 1) + 7);
+                }
+                if (k <= N - 3) {
+                    up[0] = ld(L.W(k + 1) + 6);
+                    up[1] = ld(L.W(k + 1) + 7);
+                }
+                T gu[2];
+                grad_ctrl(k, um, w + 6, up, gu);
+                gm = tmax(gm, tmax((T)fabs(gu[0]), (T)fabs(gu[1])));
+                // the rows into stage k + 1 (rowscales_at's entries, at this stage's point)
+                Lin<T> ln;
+                ln.eval(pr.c, w);
+                T tw, tv;
+                turn_d(w, w + 6, &tw, &tv);
+                jm = tmax(jm, tmax((T)fabs(w[3] * ln.st * dt), (T)fabs(ln.ct * dt)));
+                jm = tmax(jm, tmax((T)fabs(w[3] * ln.ct * dt), (T)fabs(ln.st * dt)));
+                jm = tmax(jm, tmax((T)fabs(tw), (T)fabs(tv)));
+                jm = tmax(jm, dt);
+                jm = tmax(jm, tmax((T)fabs(ln.f1), tmax((T)fabs(ln.se * dt), (T)fabs(w[3] * ln.ce * dt))));
+            }
+        }
+        T v[2] = {gm, jm};
+        const int op[2] = {RMAX, RMAX};
+        reduce<2, true>(v, op);
+        *gmax = v[0];
+        *jmax = v[1];
+    }
+    // (one copy of setup / init_point / reset_state for every mode: the cold start runs exactly
+    // init()'s stores and values)
+    MPCG_HD int init_start(const double* rec, int mode_, T mu0_) {
+        const int t = wv.lane();
+        const int nx = 8 * N - 2, nc = 6 * N;
+        const T mu0 = wv.uni_d(mu0_);
+        int used = wv.uni(mode_);
+        if (used != START_COLD) {
+            // the parts the mode reads: finite, and in FULL mode bound multipliers no less than 0
+            const bool full = used == START_FULL;
+            bool bad = !(used == START_PRIMAL || full);
+            for (int e = t; e < nx; e += 64) {
+                bad = bad || !isfinite(rec[e]);
+                if (full) {
+                    const double zl = rec[nx + e], zu = rec[2 * nx + e];
+                    bad = bad || !isfinite(zl) || !isfinite(zu) || zl < 0 || zu < 0;
+                }
+            }
+            if (full) {
+                for (int e = t; e < nc; e += 64) bad = bad || !isfinite(rec[3 * nx + e]);
+                bad = bad || !isfinite((double)mu0) || !(mu0 > (T)0);
+            }
+            if (wv.any(bad)) used = -1;
+        }
+        setup();
+        T gm = 0;
+        if (used == START_PRIMAL) {
+            // the unpushed point into W for the scaling; init_point() below replaces it
+            wv.sync();
+            for (int e = t; e < nx; e += 64) {
+                int j, k;
+                rec_var(e, &j, &k);
+                st(L.W(k) + j, (T)rec[e]);
+            }
+            wv.sync();
+            T jm;
+            scaling_at_point(&gm, &jm);
+            if (wv.uni(jm > (T)100 ? 1 : 0)) used = -2;
+            wv.sync();
+        }
+        init_point();  // (the stage table's constants, the cold point, z = 1, y = 0)
+        // (bounds selected among locals: a select between member addresses would force the
+        // solver object into scratch)
+        const T bl[3] = {sl, wl, al}, bh[3] = {su, wu, au};
+        if (used == START_PRIMAL) {
+            sf = wv.uni_d(gm > (T)100 ? (T)100 / gm : (T)1);
+            wv.sync();
+            if (t < 13) st(L.RSC() + t, 1);
+            for (int e = t; e < nx; e += 64) {
+                int j, k;
+                rec_var(e, &j, &k);
+                const T lo = j < 6 ? bl[0] : (j == 6 ? bl[1] : bl[2]);
+                const T hi = j < 6 ? bh[0] : (j == 6 ? bh[1] : bh[2]);
+                st(L.W(k) + j, push((T)rec[e], lo, hi));
+            }
+            wv.sync();
+        } else if (used == START_FULL) {
+            wv.sync();
+            for (int e = t; e < nx; e += 64) {
+                int j, k;
+                rec_var(e, &j, &k);
+                const T lo = j < 6 ? bl[0] : (j == 6 ? bl[1] : bl[2]);
+                const T hi = j < 6 ? bh[0] : (j == 6 ? bh[1] : bh[2]);
+                st(L.W(k) + j, push_k((T)rec[e], lo, hi, (T)1e-3));
+                st(L.ZL(k) + j, tmax((T)rec[nx + e] * sf, (T)1e-3));
+                st(L.ZU(k) + j, tmax((T)rec[2 * nx + e] * sf, (T)1e-3));
+            }
+            for (int e = t; e < nc; e += 64) {
+                const int j = e / N, k = e - j * N;
+                const T y = (T)rec[3 * nx + e] * sf;
+                st(L.Y(k) + j, fabs(y) > (T)1e6 ? (T)0 : y);
+            }
+            wv.sync();
+        }
+        if (used == START_FULL) {
+            reset_state(mu0, 0);
+            do_stats(false, (T)0, (T)0, K_BEGIN);
+        } else {
+            reset_state((T)P.mu_init, 0);
+            // least-squares multipliers first (constr_mult_init_max 1000)
+            do_solve(1, (T)0, K_LSQ);
+        }
+        return used;
+    }
+
     // K_LSQ: the least-squares multiplier estimate y0, used if |y0| <= 1000
     MPCG_HD int k_lsq() {
         T ymax = 0;

@@ -71,12 +71,35 @@
     X(16, 1, true, double, 1)                 \
     X(17, 1, false, double, 1)                \
     X(18, 1, false, double, 2)
+// A solve started from a solution record (include/mpcg.h mpcg_solve_device_start): the batch
+// kernel k_start_wide, general options, fp64, one per (model, horizon class) -- a parameter row
+// per problem or none is a run-time argument of the one instance -- and its resume kernels
+// k_resume_wide_start, whose overflow re-solve starts from the record again: lists and groups
+// of their own
+#define MPCG_WIDE_START_INSTANCES(X)          \
+    X(20, 0, true, double, 1, false, 2)       \
+    X(21, 0, false, double, 1, false, 2)      \
+    X(22, 0, false, double, 1, false, 1)      \
+    X(23, 0, false, double, 2, false, 1)      \
+    X(24, 1, true, double, 1, false, 2)       \
+    X(25, 1, false, double, 1, false, 2)      \
+    X(26, 1, false, double, 1, false, 1)      \
+    X(27, 1, false, double, 2, false, 1)
+#define MPCG_WIDE_START_RESUME_INSTANCES(X)   \
+    X(28, 0, true, double, 1)                 \
+    X(29, 0, false, double, 1)                \
+    X(30, 0, false, double, 2)                \
+    X(31, 1, true, double, 1)                 \
+    X(32, 1, false, double, 1)                \
+    X(33, 1, false, double, 2)
 // (an instance's name: mpcg_last_kernel() reports the one a solve launched)
 #define MPCG_SOLVE_NAME(M, S, T, NB, D, W) "k_solve_wide<" #M "," #S "," #T "," #NB "," #D "," #W ">"
 #define MPCG_WARM_NAME(M, S, T, NB, D, W) "k_warm_wide<" #M "," #S "," #T "," #NB "," #D "," #W ">"
 #define MPCG_RESUME_NAME(M, S, T, NB) "k_resume_wide<" #M "," #S "," #T "," #NB ">"
 #define MPCG_PP_SOLVE_NAME(M, S, T, NB, D, W) "k_solve_wide_pp<" #M "," #S "," #T "," #NB "," #D "," #W ">"
 #define MPCG_PP_RESUME_NAME(M, S, T, NB) "k_resume_wide_pp<" #M "," #S "," #T "," #NB ">"
+#define MPCG_START_NAME(M, S, T, NB, D, W) "k_start_wide<" #M "," #S "," #T "," #NB "," #D "," #W ">"
+#define MPCG_START_RESUME_NAME(M, S, T, NB) "k_resume_wide_start<" #M "," #S "," #T "," #NB ">"
 
 namespace mpcg {
 
@@ -112,6 +135,8 @@ inline constexpr WideKey kResumeKeys[] = {MPCG_WIDE_RESUME_INSTANCES(MPCG_KEY5)}
 inline constexpr WideKey kWarmKeys[] = {MPCG_WIDE_WARM_INSTANCES(MPCG_KEY7)};
 inline constexpr WideKey kPPSolveKeys[] = {MPCG_WIDE_PP_SOLVE_INSTANCES(MPCG_KEY7)};
 inline constexpr WideKey kPPResumeKeys[] = {MPCG_WIDE_PP_RESUME_INSTANCES(MPCG_KEY5)};
+inline constexpr WideKey kStartKeys[] = {MPCG_WIDE_START_INSTANCES(MPCG_KEY7)};
+inline constexpr WideKey kStartResumeKeys[] = {MPCG_WIDE_START_RESUME_INSTANCES(MPCG_KEY5)};
 #undef MPCG_KEY7
 #undef MPCG_KEY5
 template <size_t n>
@@ -186,6 +211,15 @@ inline WideKey pp_solve_key(const IpmParams& P, int64_t /*B*/) {
     return k;
 }
 inline WideKey pp_resume_key(const IpmParams& P) { return P.precision == 0 ? resume_key(P) : WideKey{}; }
+// A solve started from a record: the general-options fp64 instance of the horizon class (with or
+// without parameter rows), its resume kernel by the class as well; the fp32 configuration is
+// refused
+inline WideKey start_key(const IpmParams& P) {
+    const WideClass c = wide_class(P);
+    if (!c.ok || P.precision != 0) return WideKey{};
+    return WideKey{c.model, c.split, false, c.nb, false, c.one ? 1 : 2};
+}
+inline WideKey start_resume_key(const IpmParams& P) { return P.precision == 0 ? resume_key(P) : WideKey{}; }
 // the fp64 phase's instance (k_warm_wide, default options) for the horizon class of the fp64
 // parameters Pr (fp64_params): the differential drive only
 inline WideKey warm_key(const IpmParams& Pr) {

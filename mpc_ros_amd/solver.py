@@ -236,13 +236,23 @@ class BatchSolver:
 
     # ----------------------------------------------------------------- solve
     def solve(self, state: np.ndarray, coeffs: np.ndarray, want_traj: bool = True, params_rows=None,
-              want_solution: bool = False, want_gain: bool = False) -> dict:
+              want_solution: bool = False, want_gain: bool = False, start=None, start_mode=None,
+              mu0=None) -> dict:
         """params_rows [B, 16] (params.rows): a parameter row per problem instead of the handle's
         per-problem fields (mpcg_solve_pp); a row outside the parameters' domains raises.
         want_solution: also the full solution (mpcg_solve_sol) -- "sol" [B, solution_elems(N)] and
         its views "x", "zl", "zu" [B, 8N-2] and "lam" [B, 6N] (split_solution).
         want_gain (with want_solution): also the feedback gains of the records (mpcg_sens) -- "gain"
-        [B, 2, 10] and "sens_info" [B]."""
+        [B, 2, 10] and "sens_info" [B].
+        start [B, solution_elems(N)] with start_mode (an int, or [B] int32: _lib.START_COLD / _PRIMAL /
+        _FULL per problem) and mu0 (None: mu_init; a float or [B], read in FULL mode): the solve
+        started from the records (mpcg_solve_start); the result then has "start_used" [B], the mode
+        that ran (negative: the start was not usable and the problem was solved cold)."""
+        if start is not None:
+            return self._solve_start(state, coeffs, want_traj, params_rows, want_solution, want_gain, start,
+                                     start_mode, mu0)
+        if start_mode is not None or mu0 is not None:
+            raise ValueError("start_mode and mu0 need start")
         if want_gain and not want_solution:
             raise ValueError("want_gain needs want_solution: the gain is computed from the record")
         B, out, ptrs = _host_batch(state, coeffs, self.N, want_traj, diag=True)
@@ -271,14 +281,49 @@ class BatchSolver:
         # most filter entries held at once
         return out
 
+    def _solve_start(self, state, coeffs, want_traj, params_rows, want_solution, want_gain, start, start_mode, mu0):
+        if want_gain and not want_solution:
+            raise ValueError("want_gain needs want_solution: the gain is computed from the record")
+        if start_mode is None:
+            raise ValueError("start needs start_mode")
+        B, out, ptrs = _host_batch(state, coeffs, self.N, want_traj, diag=True)
+        dp, ip = C.POINTER(C.c_double), C.POINTER(C.c_int32)
+        rows = None
+        if params_rows is not None:
+            rows = np.ascontiguousarray(params_rows, dtype=np.float64)
+            assert rows.shape == (B, _lib.PP_FIELDS), "params_rows [B,16]"
+        start = np.ascontiguousarray(start, dtype=np.float64)
+        assert start.shape == (B, solution_elems(self.N)), "start [B, solution_elems(N)]"
+        mode = np.ascontiguousarray(np.broadcast_to(np.asarray(start_mode, dtype=np.int32), (B,)))
+        m0 = None if mu0 is None else np.ascontiguousarray(np.broadcast_to(np.asarray(mu0, dtype=np.float64), (B,)))
+        sol = np.zeros((B, solution_elems(self.N))) if want_solution else None
+        used = np.zeros(B, dtype=np.int32)
+        _lib.check(_lib.lib().mpcg_solve_start(
+            self._h, B, ptrs[0], ptrs[1], rows.ctypes.data_as(dp) if rows is not None else None,
+            start.ctypes.data_as(dp), mode.ctypes.data_as(ip), m0.ctypes.data_as(dp) if m0 is not None else None,
+            *ptrs[2:], sol.ctypes.data_as(dp) if sol is not None else None, used.ctypes.data_as(ip)),
+            "mpcg_solve_start")
+        out["start_used"] = used
+        if want_solution:
+            out["sol"] = sol
+            out.update(split_solution(sol, self.N))
+            if want_gain:
+                g = sens(self.params, state, coeffs, sol, params_rows=rows)
+                out["gain"], out["sens_info"] = g["gain"], g["info"]
+        return out
+
     def solve_device(self, state, coeffs, u0, traj=None, status=None, obj=None, iters=None, stream=None, diag=None,
-                     pparams=None, sol=None):
+                     pparams=None, sol=None, start=None, start_mode=None, mu0=None, start_used=None):
         """All arguments are torch tensors on this handle's GPU (float64 / int32, contiguous);
         diag [B, 4] int32: restoration phases, filter overflows, parked, filter peak.
         pparams [B, 16] float64: a parameter row per problem (mpcg_solve_device_pp), read when the
         stream runs the solve -- keep it unchanged until then.  A row outside the parameters'
         domains ends its problem with status 13, iters 0 and zero outputs.
-        sol [B, solution_elems(N)] float64: the full solution records (mpcg_solve_device_sol)."""
+        sol [B, solution_elems(N)] float64: the full solution records (mpcg_solve_device_sol).
+        start [B, solution_elems(N)] float64 with start_mode [B] int32 (an int broadcasts: a tensor
+        is made), mu0 [B] float64 or None and start_used [B] int32 or None: the solve started from the
+        records (mpcg_solve_device_start); sol may be None and may be the start tensor itself (the
+        in-place loop).  start, start_mode and mu0 are read when the stream runs the solve."""
         import torch
 
         B = state.shape[0]
@@ -292,6 +337,26 @@ class BatchSolver:
         ptr, sp = _ptr, _stream_ptr(stream, state)
         if pparams is not None:
             _on_device(pparams, (B, _lib.PP_FIELDS))
+        if start is not None:
+            if start_mode is None:
+                raise ValueError("start needs start_mode")
+            if not torch.is_tensor(start_mode):
+                start_mode = torch.full((B,), int(start_mode), dtype=torch.int32, device=state.device)
+            _on_device(start, (B, solution_elems(self.N)))
+            _on_device(start_mode, (B,), "int32")
+            if mu0 is not None:
+                _on_device(mu0, (B,))
+            if start_used is not None:
+                _on_device(start_used, (B,), "int32")
+            if sol is not None:
+                _on_device(sol, (B, solution_elems(self.N)))
+            _lib.check(_lib.lib().mpcg_solve_device_start(
+                self._h, B, ptr(state), ptr(coeffs), ptr(pparams), ptr(start), ptr(start_mode), ptr(mu0), ptr(u0),
+                ptr(traj), ptr(status), ptr(obj), ptr(iters), ptr(diag), ptr(sol), ptr(start_used), sp),
+                "mpcg_solve_device_start")
+            return
+        if start_mode is not None or mu0 is not None or start_used is not None:
+            raise ValueError("start_mode, mu0 and start_used need start")
         if sol is not None:
             _on_device(sol, (B, solution_elems(self.N)))
             _lib.check(_lib.lib().mpcg_solve_device_sol(
