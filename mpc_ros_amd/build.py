@@ -16,7 +16,7 @@ SOURCES = [os.path.join(CSRC, f) for f in ("mpcg_wide.hip", "mpcg_wide_inst.hip"
                                            "mpcg_kkt.hip", "mpcg_sens.hip",
                                            "mpcg_api.cpp", "mpcg_multi.cpp", "mpc_planner.cpp")]
 INST = os.path.join(CSRC, "mpcg_wide_inst.hip")
-N_INST = 34  # MPCG_INST groups of mpcg_wide_inst.hip (the instance lists of wide_plan.h)
+N_INST = 34  # MPCG_INST groups of mpcg_wide_inst.hip (wide_plan.h kWideGroups: the groups of its instance list)
 HEADERS = [os.path.join(CSRC, f) for f in ("ipm_core.h", "wide_core.h", "wide_plan.h", "wave_dev.h", "mpcg_internal.h",
                                            "mpcg_wide_kern.h", "mpcg_pp.h", "mpcg_window.h", "mpcg_kkt.h", "mpcg_sens.h")] + [
     os.path.join(ROOT, "include", f) for f in ("mpcg.h", "mpc_planner.h")]
@@ -77,6 +77,25 @@ def compile_units() -> list:
     return units
 
 
+def compile_flags(root: str = ROOT) -> list:
+    """The product's compiler flags, for the sources of the tree at root (tools/inst_asm.py dumps
+    another tree's instance groups with the same flags)."""
+    # (-disable-promote-alloca-to-lds: the solver owns the whole dynamic LDS from address 0;
+    # the backend would otherwise move a private array into static LDS, which the launch
+    # refuses -- mpcg_wide.hip checks sharedSizeBytes == 0)
+    return [f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC",
+            "-mllvm", "-disable-promote-alloca-to-lds", "-mllvm", "-disable-machine-licm",
+            "-Wno-unused-result", "-Wno-unused-value", "-Wno-c++20-designator",
+            f"-I{os.path.join(root, 'include')}", f"-I{os.path.join(root, 'mpc_ros_amd', 'csrc')}",
+            "-Rpass-analysis=kernel-resource-usage"]
+
+
+def is_solver_kernel(name: str) -> bool:
+    """A solver kernel instance of any kind (mangled or demangled name): the batch kernels
+    k_solve_wide, k_solve_wide_pp, k_warm_wide, k_start_wide and the resume kernel k_resume_wide."""
+    return any(k in name for k in ("k_solve_wide", "k_warm_wide", "k_start_wide", "k_resume_wide"))
+
+
 def build(force: bool = False, verbose: bool = False, jobs: int | None = None) -> str:
     import shutil
     import tempfile
@@ -84,15 +103,8 @@ def build(force: bool = False, verbose: bool = False, jobs: int | None = None) -
 
     if not force and not stale():
         return LIB
-    # (-disable-promote-alloca-to-lds: the solver owns the whole dynamic LDS from address 0;
-    # the backend would otherwise move a private array into static LDS, which the launch
-    # refuses -- mpcg_wide.hip checks sharedSizeBytes == 0)
-    flags = [f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC",
-             "-mllvm", "-disable-promote-alloca-to-lds", "-mllvm", "-disable-machine-licm",
-             "-Wno-unused-result", "-Wno-unused-value", "-Wno-c++20-designator",
-             f"-I{os.path.join(ROOT, 'include')}", f"-I{CSRC}", "-Rpass-analysis=kernel-resource-usage"]
     # (diagnostic builds only: extra compiler flags, part of the build id)
-    flags += [f'-DMPCG_BUILD_ID="MPCG-BUILD-ID:{build_id()}"'] + extra_cflags()
+    flags = compile_flags() + [f'-DMPCG_BUILD_ID="MPCG-BUILD-ID:{build_id()}"'] + extra_cflags()
     tmp = tempfile.mkdtemp(prefix="mpcg_build_")
     try:
         def cc(unit):
@@ -119,7 +131,7 @@ def build(force: bool = False, verbose: bool = False, jobs: int | None = None) -
     if verbose:
         sys.stderr.write(remarks)
     usage = kernel_resources(remarks)
-    bad = [k for k, u in usage.items() if ("k_solve_wide" in k or "k_resume_wide" in k or "k_start_wide" in k) and u.get("LDS Size [bytes/block]", 0) != 0]
+    bad = [k for k, u in usage.items() if is_solver_kernel(k) and u.get("LDS Size [bytes/block]", 0) != 0]
     if bad:
         os.remove(LIB + ".tmp")
         raise RuntimeError(f"static LDS in {bad}: the solver addresses its dynamic LDS from 0")
@@ -144,7 +156,7 @@ def save_resources(usage: dict, path: str = RESOURCES) -> None:
     restoration phase's out-of-line function, from the build's kernel-resource-usage remarks."""
     import json
 
-    keep = {k: v for k, v in usage.items() if "k_solve_wide" in k or "k_resume_wide" in k or "k_start_wide" in k or "resto_phase" in k}
+    keep = {k: v for k, v in usage.items() if is_solver_kernel(k) or "resto_phase" in k}
     names = demangle(sorted(keep))
     os.makedirs(os.path.dirname(path), exist_ok=True)
     with open(path, "w") as f:

@@ -446,17 +446,14 @@ static int lds_refusal(const mpcg_handle* h) {
     return fail(-1, "STEPS must be <= 128 (the problem state must fit the CU's 160 KiB of LDS)");
 }
 
-// Queues the solve on s; d_pparams: a parameter row per problem or null.  The caller has passed
-// the refusals, grown the solver's scratch (ensure_solve) and ordered s (with_scratch).
-static int queue_solve(mpcg_handle* h, int64_t B, const double* d_state, const double* d_coeffs,
-                       const double* d_pparams, double* d_u0, double* d_traj, int32_t* d_status, double* d_obj,
-                       int32_t* d_iters, int32_t* d_diag, hipStream_t s, double* d_sol = nullptr,
-                       const mpcg::WideStart* start = nullptr) {
+// Queues the solve of a request (device pointers) on s.  The caller has passed the refusals,
+// grown the solver's scratch (ensure_solve) and ordered s (with_scratch).
+static int queue_solve(mpcg_handle* h, const mpcg::SolveRequest& rq, hipStream_t s) {
     // batches larger than the resident wavefronts (8 per CU) are solved in
     // expected-longest-first order (launch_wide_order)
     int32_t* order = nullptr;
-    if (B > kOrderMinBatch) {
-        hipError_t e = mpcg::launch_wide_order(B, d_coeffs, h->d_sched.p, h->d_sched.bytes, &order, s);
+    if (rq.B > kOrderMinBatch) {
+        hipError_t e = mpcg::launch_wide_order(rq.B, rq.coeffs, h->d_sched.p, h->d_sched.bytes, &order, s);
         if (e != hipSuccess) return hip_fail(e, "solve-order sort");
     }
     mpcg::WideStreams ws;
@@ -465,9 +462,8 @@ static int queue_solve(mpcg_handle* h, int64_t B, const double* d_state, const d
     ws.ev_fork = h->ev_fork;
     ws.ev_join = h->ev_join;
     ws.ev_join2 = h->ev_join2;
-    hipError_t e = mpcg::launch_wide_solve(handle_ipm(h), B, d_state, d_coeffs, d_u0, d_traj, d_status, d_obj, d_iters,
-                                           d_diag, order, h->d_spill.p, h->d_spill.bytes, s, ws, &h->last_kernel,
-                                           d_pparams, d_sol, start);
+    hipError_t e = mpcg::launch_wide_solve(handle_ipm(h), rq, order, h->d_spill.p, h->d_spill.bytes, s, ws,
+                                           &h->last_kernel);
     if (e != hipSuccess) return hip_fail(e, "wide solve launch");
     h->last_ordered = order != nullptr;
     return 0;
@@ -475,152 +471,71 @@ static int queue_solve(mpcg_handle* h, int64_t B, const double* d_state, const d
 
 static const char kNoFp32Sol[] =
     "precision 1 with no_restoration 1 (the fp32 phase alone) has no fp64 ending to report: no solution record";
+static const char kNoFp32Start[] = "precision 1 (fp32) takes no start point: the started solve has fp64 instances only";
 
-// the device solve; d_pparams: a parameter row per problem (mpcg_solve_device_pp) or null;
-// want_sol (mpcg_solve_device_sol): the solution records into d_sol
-static int solve_device(mpcg_handle* h, int64_t B, const double* d_state, const double* d_coeffs,
-                        const double* d_pparams, double* d_u0, double* d_traj, int32_t* d_status, double* d_obj,
-                        int32_t* d_iters, int32_t* d_diag, void* stream, double* d_sol = nullptr,
-                        bool want_sol = false) {
-    int rc = batch_check(h, B);
+// The refusals of a solve request that the device and the host entries share, in their order
+// (host: the arrays are the caller's own).  want_sol (mpcg_solve_device_sol, mpcg_solve_sol): the
+// records are required.  1: nothing to do (B = 0).
+static int request_refusal(const mpcg_handle* h, const mpcg::SolveRequest& rq, bool want_sol, bool host) {
+    int rc = batch_check(h, rq.B);
     if (rc) return rc;
-    if (want_sol && !d_sol) return fail(-1, "sol is required");
-    if (B == 0) return 0;
-    if (!d_state || !d_coeffs || !d_u0) return fail(-1, "state, coeffs and u0 are required");
-    rc = params_refusal(h, d_pparams != nullptr);
+    if (want_sol && !rq.sol) return fail(-1, "sol is required");
+    if (rq.started() && h->params.precision != 0) return fail(-1, kNoFp32Start);
+    if (rq.B == 0) return 1;
+    if (!rq.state || !rq.coeffs || !rq.u0) return fail(-1, "state, coeffs and u0 are required");
+    // (fp32 with rows is refused before fp32 without an fp64 ending by the device entries, after it
+    // by the host entries, which then read the rows: the order each always had)
+    rc = params_refusal(h, !host && rq.rows);
     if (rc) return rc;
     if (want_sol && h->params.precision == 1 && h->params.no_restoration == 1) return fail(-1, kNoFp32Sol);
+    if (!host || !rq.rows) return 0;
+    if (h->params.precision != 0) return fail(-1, kNoFp32Rows);
+    return mpcg_pparams_check(rq.rows, rq.B, h->params.model, nullptr);
+}
+
+// the device solve of a request, for every device entry
+static int solve_device(mpcg_handle* h, const mpcg::SolveRequest& rq, void* stream, bool want_sol = false) {
+    int rc = request_refusal(h, rq, want_sol, false);
+    if (rc) return rc < 0 ? rc : 0;
     hipError_t e = hipSetDevice(h->device);
     if (e != hipSuccess) return hip_fail(e, "hipSetDevice");
     hipStream_t s = (hipStream_t)stream;  // NULL = the null stream, as in HIP
     rc = lds_refusal(h);
-    if (rc == 0) rc = ensure_solve(h, B);
+    if (rc == 0) rc = ensure_solve(h, rq.B);
     if (rc) return rc;
-    return with_scratch(h, s, [&] {
-        return queue_solve(h, B, d_state, d_coeffs, d_pparams, d_u0, d_traj, d_status, d_obj, d_iters, d_diag, s,
-                           d_sol);
-    });
+    return with_scratch(h, s, [&] { return queue_solve(h, rq, s); });
 }
 
 int mpcg_solve_device_ex(mpcg_handle* h, int64_t B, const double* d_state, const double* d_coeffs, double* d_u0,
                          double* d_traj, int32_t* d_status, double* d_obj, int32_t* d_iters, int32_t* d_diag,
                          void* stream) {
-    return solve_device(h, B, d_state, d_coeffs, nullptr, d_u0, d_traj, d_status, d_obj, d_iters, d_diag, stream);
+    return solve_device(h, {B, d_state, d_coeffs, nullptr, d_u0, d_traj, d_status, d_obj, d_iters, d_diag}, stream);
 }
 
 int mpcg_solve_device_pp(mpcg_handle* h, int64_t B, const double* d_state, const double* d_coeffs,
                          const double* d_pparams, double* d_u0, double* d_traj, int32_t* d_status, double* d_obj,
                          int32_t* d_iters, int32_t* d_diag, void* stream) {
     if (B > 0 && !d_pparams) return fail(-1, "pparams is required");
-    return solve_device(h, B, d_state, d_coeffs, d_pparams, d_u0, d_traj, d_status, d_obj, d_iters, d_diag, stream);
+    return solve_device(h, {B, d_state, d_coeffs, d_pparams, d_u0, d_traj, d_status, d_obj, d_iters, d_diag}, stream);
 }
 
 int mpcg_solve_device_sol(mpcg_handle* h, int64_t B, const double* d_state, const double* d_coeffs,
                           const double* d_pparams, double* d_u0, double* d_traj, int32_t* d_status, double* d_obj,
                           int32_t* d_iters, int32_t* d_diag, double* d_sol, void* stream) {
-    return solve_device(h, B, d_state, d_coeffs, d_pparams, d_u0, d_traj, d_status, d_obj, d_iters, d_diag, stream,
-                        d_sol, true);
+    return solve_device(h, {B, d_state, d_coeffs, d_pparams, d_u0, d_traj, d_status, d_obj, d_iters, d_diag, d_sol},
+                        stream, true);
 }
 
 // ---- start point in ----
-static const char kNoFp32Start[] = "precision 1 (fp32) takes no start point: the started solve has fp64 instances only";
-
 int mpcg_solve_device_start(mpcg_handle* h, int64_t B, const double* d_state, const double* d_coeffs,
                             const double* d_pparams, const double* d_start, const int32_t* d_start_mode,
                             const double* d_mu0, double* d_u0, double* d_traj, int32_t* d_status, double* d_obj,
                             int32_t* d_iters, int32_t* d_diag, double* d_sol, int32_t* d_start_used, void* stream) {
     // (the start first: an argument check that needs no handle)
     if (!d_start || !d_start_mode) return fail(-1, "start and start_mode are required");
-    int rc = batch_check(h, B);
-    if (rc) return rc;
-    if (h->params.precision != 0) return fail(-1, kNoFp32Start);
-    if (B == 0) return 0;
-    if (!d_state || !d_coeffs || !d_u0) return fail(-1, "state, coeffs and u0 are required");
-    rc = params_refusal(h, d_pparams != nullptr);
-    if (rc) return rc;
-    hipError_t e = hipSetDevice(h->device);
-    if (e != hipSuccess) return hip_fail(e, "hipSetDevice");
-    hipStream_t s = (hipStream_t)stream;
-    rc = lds_refusal(h);
-    if (rc == 0) rc = ensure_solve(h, B);
-    if (rc) return rc;
-    const mpcg::WideStart st{d_start, d_start_mode, d_mu0, d_start_used};
-    return with_scratch(h, s, [&] {
-        return queue_solve(h, B, d_state, d_coeffs, d_pparams, d_u0, d_traj, d_status, d_obj, d_iters, d_diag, s,
-                           d_sol, &st);
-    });
-}
-
-int mpcg_solve_start(mpcg_handle* h, int64_t B, const double* state, const double* coeffs, const double* pparams,
-                     const double* start, const int32_t* start_mode, const double* mu0, double* u0, double* traj,
-                     int32_t* status, double* obj, int32_t* iters, int32_t* diag, double* sol, int32_t* start_used) {
-    if (!start || !start_mode) return fail(-1, "start and start_mode are required");
-    int rc = batch_check(h, B);
-    if (rc) return rc;
-    if (h->params.precision != 0) return fail(-1, kNoFp32Start);
-    if (B == 0) return 0;
-    if (!state || !coeffs || !u0) return fail(-1, "state, coeffs and u0 are required");
-    rc = mpcg_params_check(&h->params);
-    if (rc) return rc;
-    if (pparams) {
-        rc = mpcg_pparams_check(pparams, B, h->params.model, nullptr);
-        if (rc) return rc;
-    }
-    const int N = h->params.steps;
-    // io block (doubles): state 6 | coeffs 4 | u0 2 | traj 3N | obj 1 | mu0 1 | the records (start
-    // in, the solution out in place) | the parameter rows 16 | then int32: status, iters, mode,
-    // used, diag 4
-    const size_t ne = (size_t)mpcg::solution_elems(N), nb = (size_t)B;
-    const size_t nd = (size_t)(6 + 4 + 2 + 3 * N + 1 + 1) + ne + (pparams ? MPCG_PP_FIELDS : 0);
-    const size_t need = (nd * sizeof(double) + 8 * sizeof(int32_t)) * nb;
-    hipError_t e = hipSetDevice(h->device);
-    if (e != hipSuccess) return hip_fail(e, "hipSetDevice");
-    rc = ensure(h, h->d_io, need, "hipMalloc(io)");
-    if (rc) return rc;
-    double* ds = (double*)h->d_io.p;
-    double* dc = ds + 6 * nb;
-    double* du = dc + 4 * nb;
-    double* dt = du + 2 * nb;
-    double* dob = dt + (size_t)3 * N * nb;
-    double* dmu = dob + nb;
-    double* drec = dmu + nb;
-    double* dpp = drec + ne * nb;
-    int32_t* dst = (int32_t*)(dpp + (pparams ? (size_t)MPCG_PP_FIELDS * nb : 0));
-    int32_t* dit = dst + nb;
-    int32_t* dmd = dit + nb;
-    int32_t* dus = dmd + nb;
-    int32_t* ddg = dus + nb;
-    e = hipMemcpyAsync(ds, state, sizeof(double) * 6 * nb, hipMemcpyHostToDevice, h->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(dc, coeffs, sizeof(double) * 4 * nb, hipMemcpyHostToDevice, h->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(drec, start, sizeof(double) * ne * nb, hipMemcpyHostToDevice, h->stream);
-    if (e == hipSuccess)
-        e = hipMemcpyAsync(dmd, start_mode, sizeof(int32_t) * nb, hipMemcpyHostToDevice, h->stream);
-    if (e == hipSuccess && mu0) e = hipMemcpyAsync(dmu, mu0, sizeof(double) * nb, hipMemcpyHostToDevice, h->stream);
-    if (e == hipSuccess && pparams)
-        e = hipMemcpyAsync(dpp, pparams, sizeof(double) * MPCG_PP_FIELDS * nb, hipMemcpyHostToDevice, h->stream);
-    if (e != hipSuccess) return hip_fail(e, "hipMemcpy H2D");
-    // (the records are solved in place on the device: sol aliases start there)
-    rc = mpcg_solve_device_start(h, B, ds, dc, pparams ? dpp : nullptr, drec, dmd, mu0 ? dmu : nullptr, du, dt, dst,
-                                 dob, dit, diag ? ddg : nullptr, sol ? drec : nullptr, dus, h->stream);
-    if (rc) return rc;
-    e = hipMemcpyAsync(u0, du, sizeof(double) * 2 * nb, hipMemcpyDeviceToHost, h->stream);
-    if (e == hipSuccess && traj)
-        e = hipMemcpyAsync(traj, dt, sizeof(double) * 3 * N * nb, hipMemcpyDeviceToHost, h->stream);
-    if (e == hipSuccess && obj) e = hipMemcpyAsync(obj, dob, sizeof(double) * nb, hipMemcpyDeviceToHost, h->stream);
-    if (e == hipSuccess && status)
-        e = hipMemcpyAsync(status, dst, sizeof(int32_t) * nb, hipMemcpyDeviceToHost, h->stream);
-    if (e == hipSuccess && iters)
-        e = hipMemcpyAsync(iters, dit, sizeof(int32_t) * nb, hipMemcpyDeviceToHost, h->stream);
-    if (e == hipSuccess && diag)
-        e = hipMemcpyAsync(diag, ddg, sizeof(int32_t) * 4 * nb, hipMemcpyDeviceToHost, h->stream);
-    if (e == hipSuccess && start_used)
-        e = hipMemcpyAsync(start_used, dus, sizeof(int32_t) * nb, hipMemcpyDeviceToHost, h->stream);
-    if (e == hipSuccess && sol)
-        e = hipMemcpyAsync(sol, drec, sizeof(double) * ne * nb, hipMemcpyDeviceToHost, h->stream);
-    if (e != hipSuccess) return hip_fail(e, "hipMemcpy D2H");
-    e = hipStreamSynchronize(h->stream);
-    if (e != hipSuccess) return hip_fail(e, "hipStreamSynchronize");
-    return 0;
+    return solve_device(h, {B, d_state, d_coeffs, d_pparams, d_u0, d_traj, d_status, d_obj, d_iters, d_diag, d_sol,
+                            {d_start, d_start_mode, d_mu0, d_start_used}},
+                        stream);
 }
 
 int64_t mpcg_solution_elems(int32_t N) { return N >= 2 ? mpcg::solution_elems(N) : 0; }
@@ -630,73 +545,76 @@ int mpcg_solve(mpcg_handle* h, int64_t B, const double* state, const double* coe
     return mpcg_solve_ex(h, B, state, coeffs, u0, traj, status, obj, iters, nullptr);
 }
 
-// the host solve; pparams: a parameter row per problem (mpcg_solve_pp) or null
-static int solve_host(mpcg_handle* h, int64_t B, const double* state, const double* coeffs, const double* pparams,
-                      double* u0, double* traj, int32_t* status, double* obj, int32_t* iters, int32_t* diag,
-                      double* sol = nullptr, bool want_sol = false) {
-    int rc = batch_check(h, B);
-    if (rc) return rc;
-    if (want_sol && !sol) return fail(-1, "sol is required");
-    if (B == 0) return 0;
-    if (!state || !coeffs || !u0) return fail(-1, "state, coeffs and u0 are required");
-    rc = mpcg_params_check(&h->params);
-    if (rc) return rc;
-    if (want_sol && h->params.precision == 1 && h->params.no_restoration == 1) return fail(-1, kNoFp32Sol);
-    if (pparams) {
-        if (h->params.precision != 0) return fail(-1, kNoFp32Rows);
-        rc = mpcg_pparams_check(pparams, B, h->params.model, nullptr);
-        if (rc) return rc;
-    }
+// The host solve of a request whose arrays are the caller's own, for every host entry: staged
+// through the handle's io block (wide_plan.h IoLayout), solved by solve_device on the handle's
+// stream, copied back.  With a start the records are solved in place on the device: sol aliases
+// the start records there.
+static int solve_host(mpcg_handle* h, const mpcg::SolveRequest& host, bool want_sol = false) {
+    int rc = request_refusal(h, host, want_sol, true);
+    if (rc) return rc < 0 ? rc : 0;
     const int N = h->params.steps;
-    // io block: state 6 | coeffs 4 | u0 2 | traj 3N | obj 1 | status+iters (2 int32 = 1 double) |
-    // diag (4 int32 = 2 doubles) | the parameter rows 16 (mpcg_solve_pp) | the solution records
-    // (mpcg_solve_sol)
-    const size_t nsol = want_sol ? (size_t)mpcg::solution_elems(N) : 0;
-    const size_t per = (size_t)(6 + 4 + 2 + 3 * N + 1 + 1 + 2) + (pparams ? MPCG_PP_FIELDS : 0) + nsol;
-    const size_t need = per * sizeof(double) * (size_t)B;
+    const bool st = host.started();
+    const mpcg::IoLayout L(host.B, N, host.rows != nullptr, host.sol != nullptr, st);
     hipError_t e = hipSetDevice(h->device);
     if (e != hipSuccess) return hip_fail(e, "hipSetDevice");
-    rc = ensure(h, h->d_io, need, "hipMalloc(io)");
+    rc = ensure(h, h->d_io, L.total, "hipMalloc(io)");
     if (rc) return rc;
-    double* ds = (double*)h->d_io.p;
-    double* dc = ds + 6 * B;
-    double* du = dc + 4 * B;
-    double* dt = du + 2 * B;
-    double* dob = dt + (size_t)3 * N * B;
-    int32_t* dst = (int32_t*)(dob + B);
-    int32_t* dit = dst + B;
-    int32_t* ddg = dit + B;
-    double* dpp = (double*)(ddg + 4 * B);
-    double* dsol = dpp + (pparams ? (size_t)MPCG_PP_FIELDS * B : 0);
-    e = hipMemcpyAsync(ds, state, sizeof(double) * 6 * B, hipMemcpyHostToDevice, h->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(dc, coeffs, sizeof(double) * 4 * B, hipMemcpyHostToDevice, h->stream);
-    if (e == hipSuccess && pparams)
-        e = hipMemcpyAsync(dpp, pparams, sizeof(double) * MPCG_PP_FIELDS * B, hipMemcpyHostToDevice, h->stream);
+    // (region, the caller's array in, the caller's array out, bytes: null arrays are not copied)
+    struct Xfer {
+        const mpcg::Region& r;
+        const void* in;
+        void* out;
+        size_t bytes;
+    };
+    const size_t d = sizeof(double) * (size_t)host.B, i = sizeof(int32_t) * (size_t)host.B;
+    const Xfer xfers[] = {{L.state, host.state, nullptr, 6 * d},
+                          {L.coeffs, host.coeffs, nullptr, 4 * d},
+                          {L.rows, host.rows, nullptr, MPCG_PP_FIELDS * d},
+                          {L.rec, host.start.rec, host.sol, (size_t)mpcg::solution_elems(N) * d},
+                          {L.mu0, host.start.mu0, nullptr, d},
+                          {L.mode, host.start.mode, nullptr, i},
+                          {L.u0, nullptr, host.u0, 2 * d},
+                          {L.traj, nullptr, host.traj, 3 * (size_t)N * d},
+                          {L.obj, nullptr, host.obj, d},
+                          {L.status, nullptr, host.status, i},
+                          {L.iters, nullptr, host.iters, i},
+                          {L.diag, nullptr, host.diag, 4 * i},
+                          {L.used, nullptr, host.start.used, i}};
+    for (const Xfer& x : xfers)
+        if (e == hipSuccess && x.in)
+            e = hipMemcpyAsync(h->d_io.at<char>(x.r), x.in, x.bytes, hipMemcpyHostToDevice, h->stream);
     if (e != hipSuccess) return hip_fail(e, "hipMemcpy H2D");
-    rc = solve_device(h, B, ds, dc, pparams ? dpp : nullptr, du, dt, dst, dob, dit, diag ? ddg : nullptr, h->stream,
-                      want_sol ? dsol : nullptr, want_sol);
+    const DevBuf& io = h->d_io;
+    const mpcg::SolveRequest dev{host.B, io.at<double>(L.state), io.at<double>(L.coeffs),
+                                 host.rows ? io.at<double>(L.rows) : nullptr, io.at<double>(L.u0),
+                                 io.at<double>(L.traj), io.at<int32_t>(L.status), io.at<double>(L.obj),
+                                 io.at<int32_t>(L.iters), host.diag ? io.at<int32_t>(L.diag) : nullptr,
+                                 host.sol ? io.at<double>(L.rec) : nullptr,
+                                 {st ? io.at<double>(L.rec) : nullptr, st ? io.at<int32_t>(L.mode) : nullptr,
+                                  host.start.mu0 ? io.at<double>(L.mu0) : nullptr,
+                                  st ? io.at<int32_t>(L.used) : nullptr}};
+    rc = solve_device(h, dev, h->stream, want_sol);
     if (rc) return rc;
-    e = hipMemcpyAsync(u0, du, sizeof(double) * 2 * B, hipMemcpyDeviceToHost, h->stream);
-    if (e == hipSuccess && traj)
-        e = hipMemcpyAsync(traj, dt, sizeof(double) * 3 * N * B, hipMemcpyDeviceToHost, h->stream);
-    if (e == hipSuccess && obj) e = hipMemcpyAsync(obj, dob, sizeof(double) * B, hipMemcpyDeviceToHost, h->stream);
-    if (e == hipSuccess && status)
-        e = hipMemcpyAsync(status, dst, sizeof(int32_t) * B, hipMemcpyDeviceToHost, h->stream);
-    if (e == hipSuccess && iters)
-        e = hipMemcpyAsync(iters, dit, sizeof(int32_t) * B, hipMemcpyDeviceToHost, h->stream);
-    if (e == hipSuccess && diag)
-        e = hipMemcpyAsync(diag, ddg, sizeof(int32_t) * 4 * B, hipMemcpyDeviceToHost, h->stream);
-    if (e == hipSuccess && want_sol)
-        e = hipMemcpyAsync(sol, dsol, sizeof(double) * nsol * B, hipMemcpyDeviceToHost, h->stream);
+    for (const Xfer& x : xfers)
+        if (e == hipSuccess && x.out)
+            e = hipMemcpyAsync(x.out, h->d_io.at<char>(x.r), x.bytes, hipMemcpyDeviceToHost, h->stream);
     if (e != hipSuccess) return hip_fail(e, "hipMemcpy D2H");
     e = hipStreamSynchronize(h->stream);
     if (e != hipSuccess) return hip_fail(e, "hipStreamSynchronize");
     return 0;
 }
 
+int mpcg_solve_start(mpcg_handle* h, int64_t B, const double* state, const double* coeffs, const double* pparams,
+                     const double* start, const int32_t* start_mode, const double* mu0, double* u0, double* traj,
+                     int32_t* status, double* obj, int32_t* iters, int32_t* diag, double* sol, int32_t* start_used) {
+    if (!start || !start_mode) return fail(-1, "start and start_mode are required");
+    return solve_host(h, {B, state, coeffs, pparams, u0, traj, status, obj, iters, diag, sol,
+                          {start, start_mode, mu0, start_used}});
+}
+
 int mpcg_solve_sol(mpcg_handle* h, int64_t B, const double* state, const double* coeffs, const double* pparams,
                    double* u0, double* traj, int32_t* status, double* obj, int32_t* iters, int32_t* diag, double* sol) {
-    return solve_host(h, B, state, coeffs, pparams, u0, traj, status, obj, iters, diag, sol, true);
+    return solve_host(h, {B, state, coeffs, pparams, u0, traj, status, obj, iters, diag, sol}, true);
 }
 
 // ---- the KKT certificate (mpcg_kkt.h) ----
@@ -816,13 +734,13 @@ int mpcg_sens_apply_device(mpcg_handle* h, int64_t B, const double* d_pparams, c
 
 int mpcg_solve_ex(mpcg_handle* h, int64_t B, const double* state, const double* coeffs, double* u0, double* traj,
                   int32_t* status, double* obj, int32_t* iters, int32_t* diag) {
-    return solve_host(h, B, state, coeffs, nullptr, u0, traj, status, obj, iters, diag);
+    return solve_host(h, {B, state, coeffs, nullptr, u0, traj, status, obj, iters, diag});
 }
 
 int mpcg_solve_pp(mpcg_handle* h, int64_t B, const double* state, const double* coeffs, const double* pparams,
                   double* u0, double* traj, int32_t* status, double* obj, int32_t* iters, int32_t* diag) {
     if (B > 0 && !pparams) return fail(-1, "pparams is required");
-    return solve_host(h, B, state, coeffs, pparams, u0, traj, status, obj, iters, diag);
+    return solve_host(h, {B, state, coeffs, pparams, u0, traj, status, obj, iters, diag});
 }
 
 int mpcg_pparams_fill(const mpcg_params* p, int64_t B, double* rows) {
@@ -923,7 +841,7 @@ static int ensure_tick(mpcg_handle* h, const mpcg::TickLayout& L, int64_t B, int
 static int tick(mpcg_handle* h, const Tick& t, const mpcg::TickLayout& L, hipStream_t s) {
     double *st = h->d_tick.at<double>(L.state), *cf = h->d_tick.at<double>(L.coeffs), *u0 = h->d_tick.at<double>(L.u0);
     int rc = queue_preprocess(h, t.B, t.M, t.count, t.pose, t.vel, t.plan, t.delay_mode, st, cf, s);
-    if (rc == 0) rc = queue_solve(h, t.B, st, cf, t.rows, u0, t.traj, t.status, nullptr, t.iters, nullptr, s);
+    if (rc == 0) rc = queue_solve(h, {t.B, st, cf, t.rows, u0, t.traj, t.status, nullptr, t.iters}, s);
     if (rc) return rc;
     hipError_t e = mpcg::launch_post(t.B, h->params.dt, h->params.ref_v, t.ref_v, t.vel, u0, t.cmd, s);
     return e == hipSuccess ? 0 : hip_fail(e, "post-processing launch");

@@ -32,23 +32,35 @@ struct WideStreams {
 };
 // A started solve (mpcg_solve_device_start): the start records [B][solution_elems(N)], the mode
 // of each problem, the barrier parameter of each FULL start (or null: mu_init) and the mode that
-// ran (or null), all on the device -- the k_start_wide / k_resume_wide_start instances; fp64 only
+// ran (or null), all on the device -- the k_start_wide / k_resume_wide<START_RESUME> instances;
+// fp64 only
 struct WideStart {
     const double* rec = nullptr;
     const int32_t* mode = nullptr;
     const double* mu0 = nullptr;
     int32_t* used = nullptr;
 };
-hipError_t launch_wide_solve(const IpmParams& P, int64_t B, const double* state, const double* coeffs, double* u0,
-                             double* traj, int32_t* status, double* obj, int32_t* iters, int32_t* diag,
-                             const int32_t* order, void* spill, size_t spill_bytes, hipStream_t stream,
-                             const WideStreams& ws = WideStreams(), const char** kernel_name = nullptr,
-                             const double* pparams = nullptr, double* sol = nullptr,
-                             const WideStart* start = nullptr);
-// (pparams: a parameter row per problem, [B][16] doubles in include/mpcg.h's MPCG_PP_* order,
-// on the device -- the k_solve_wide_pp / k_resume_wide_pp instances; fp64 only)
-// (sol: the solution records [B][solution_elems(N)] on the device, written by every ending's
-// write_out -- WideSolver::solution_out -- or null)
+// What one solve of B problems reads and writes, all on the device.  Required: state [B][6],
+// coeffs [B][4], u0 [B][2]; every other pointer may be null.
+struct SolveRequest {
+    int64_t B = 0;
+    const double *state = nullptr, *coeffs = nullptr;
+    // a parameter row per problem, [B][16] doubles in include/mpcg.h's MPCG_PP_* order -- the
+    // k_solve_wide_pp / k_resume_wide<PP_RESUME> instances; fp64 only
+    const double* rows = nullptr;
+    double *u0 = nullptr, *traj = nullptr;  // traj [B][3][N]
+    int32_t* status = nullptr;
+    double* obj = nullptr;
+    int32_t *iters = nullptr, *diag = nullptr;  // diag [B][4]
+    // the solution records [B][solution_elems(N)], written by every ending's write_out --
+    // WideSolver::solution_out (may be start.rec: a record is read before its problem's solve)
+    double* sol = nullptr;
+    WideStart start;  // (rec and mode given: a started solve)
+    bool started() const { return start.rec || start.mode; }
+};
+hipError_t launch_wide_solve(const IpmParams& P, const SolveRequest& rq, const int32_t* order, void* spill,
+                             size_t spill_bytes, hipStream_t stream, const WideStreams& ws = WideStreams(),
+                             const char** kernel_name = nullptr);
 // The certificate (mpcg_kkt.hip): cert [B][4] from the NLP alone at the records sol; `row` the
 // handle's per-problem fields, rows [B][16] (or null) a row per problem.
 struct PPRow;

@@ -1,7 +1,7 @@
 // mpc_ros_amd/csrc/mpcg_pp.h -- per-problem parameter rows (include/mpcg.h MPCG_PP_*): a row's
 // domain check and its fields as IpmParams, a row by value (PPRow) and a robot's row written from
 // the handle's, and Tracking::deceleration's rule.  Host and device: mpcg_api.cpp
-// (mpcg_pparams_check, mpcg_decelerate) and the kernels (k_solve_wide_pp, k_resume_wide_pp,
+// (mpcg_pparams_check, mpcg_decelerate) and the kernels (k_solve_wide_pp, k_resume_wide<PP_RESUME>,
 // k_decelerate, k_rollout_begin) run the same code.
 #ifndef MPCG_PP_H
 #define MPCG_PP_H

@@ -5,6 +5,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdlib>
+#include <utility>
 #include <hipcub/device/device_radix_sort.hpp>
 
 #include "mpcg_wide_kern.h"
@@ -61,65 +62,31 @@ hipError_t launch_wide_order(int64_t B, const double* coeffs, void* buf, size_t 
     return e;
 }
 
-// The instances (solve_kernel_fn / warm_kernel_fn / resume_kernel_fn, mpcg_wide_inst.hip) by key:
-// one table per list of wide_plan.h.  A diagnostic build with MPCG_HEADLINE_ONLY links only the
-// benchmark configuration's groups (tools/build_wt.sh): every other instance is null.
+// The kernels of wide_plan.h's rows, row by row: filled once, by every group's wide_group
+// (mpcg_wide_inst.hip).  A diagnostic build with MPCG_HEADLINE_ONLY links only the benchmark
+// configuration's groups, 0 and 1 (tools/build_wt.sh): every other row stays null.
 #ifdef MPCG_HEADLINE_ONLY
-constexpr bool kHeadlineOnly = true;
+constexpr int kLinkedGroups = 2;
 #else
-constexpr bool kHeadlineOnly = false;
+constexpr int kLinkedGroups = kWideGroups;
 #endif
-enum InstKind { SOLVE, WARM, RESUME, PP_SOLVE, PP_RESUME, START_SOLVE, START_RESUME };
-template <int KIND, int M, bool S, class T, int NB, bool D, int W>
-static const void* inst_fn() {
-    if constexpr (kHeadlineOnly && !((KIND == SOLVE || KIND == RESUME) && M == 0 && S && sizeof(T) == 8 && NB == 1 && D))
-        return nullptr;
-    else if constexpr (KIND == SOLVE)
-        return solve_kernel_fn<M, S, T, NB, D, W>();
-    else if constexpr (KIND == WARM)
-        return warm_kernel_fn<M, S, T, NB, D, W>();
-    else if constexpr (KIND == PP_SOLVE)
-        return pp_solve_kernel_fn<M, S, T, NB, D, W>();
-    else if constexpr (KIND == PP_RESUME)
-        return pp_resume_kernel_fn<M, S, T, NB>();
-    else if constexpr (KIND == START_SOLVE)
-        return start_kernel_fn<M, S, T, NB, D, W>();
-    else if constexpr (KIND == START_RESUME)
-        return start_resume_kernel_fn<M, S, T, NB>();
-    else
-        return resume_kernel_fn<M, S, T, NB>();
+template <int... G>
+static void fill_groups(const void** t, std::integer_sequence<int, G...>) {
+    (wide_group<G>(t), ...);
 }
-// (the tables: one entry per key of wide_plan.h's kSolveKeys / kWarmKeys / kResumeKeys, in their order)
-#define MPCG_ENT_SOLVE(g, M, S, T, NB, D, W) {inst_fn<SOLVE, M, S, T, NB, D, W>(), MPCG_SOLVE_NAME(M, S, T, NB, D, W)},
-#define MPCG_ENT_WARM(g, M, S, T, NB, D, W) {inst_fn<WARM, M, S, T, NB, D, W>(), MPCG_WARM_NAME(M, S, T, NB, D, W)},
-#define MPCG_ENT_RESUME(g, M, S, T, NB) {inst_fn<RESUME, M, S, T, NB, true, 0>(), MPCG_RESUME_NAME(M, S, T, NB)},
-static const WideInst kSolveInst[] = {MPCG_WIDE_SOLVE_INSTANCES(MPCG_ENT_SOLVE)};
-static const WideInst kWarmInst[] = {MPCG_WIDE_WARM_INSTANCES(MPCG_ENT_WARM)};
-static const WideInst kResumeInst[] = {MPCG_WIDE_RESUME_INSTANCES(MPCG_ENT_RESUME)};
-// (the per-problem instances: kPPSolveKeys / kPPResumeKeys)
-#define MPCG_ENT_PP_SOLVE(g, M, S, T, NB, D, W) \
-    {inst_fn<PP_SOLVE, M, S, T, NB, D, W>(), MPCG_PP_SOLVE_NAME(M, S, T, NB, D, W)},
-#define MPCG_ENT_PP_RESUME(g, M, S, T, NB) {inst_fn<PP_RESUME, M, S, T, NB, true, 0>(), MPCG_PP_RESUME_NAME(M, S, T, NB)},
-static const WideInst kPPSolveInst[] = {MPCG_WIDE_PP_SOLVE_INSTANCES(MPCG_ENT_PP_SOLVE)};
-static const WideInst kPPResumeInst[] = {MPCG_WIDE_PP_RESUME_INSTANCES(MPCG_ENT_PP_RESUME)};
-// (the started solve's instances: kStartKeys / kStartResumeKeys)
-#define MPCG_ENT_START(g, M, S, T, NB, D, W) {inst_fn<START_SOLVE, M, S, T, NB, D, W>(), MPCG_START_NAME(M, S, T, NB, D, W)},
-#define MPCG_ENT_START_RESUME(g, M, S, T, NB) \
-    {inst_fn<START_RESUME, M, S, T, NB, true, 0>(), MPCG_START_RESUME_NAME(M, S, T, NB)},
-static const WideInst kStartInst[] = {MPCG_WIDE_START_INSTANCES(MPCG_ENT_START)};
-static const WideInst kStartResumeInst[] = {MPCG_WIDE_START_RESUME_INSTANCES(MPCG_ENT_START_RESUME)};
 // the instance of a key; fn null: the key is none (refused parameters) or not in the library
-template <size_t n>
-static WideInst find_inst(const WideKey (&keys)[n], const WideInst (&inst)[n], const WideKey& k) {
-    for (size_t i = 0; i < n; ++i)
-        if (keys[i] == k) return inst[i];
-    return WideInst{nullptr, ""};
+static WideInst find_inst(const WideKey& k) {
+    static const void* const* table = [] {
+        static const void* t[kWideInstances] = {};
+        fill_groups(t, std::make_integer_sequence<int, kLinkedGroups>());
+        return t;
+    }();
+    const int i = k.ok() ? find_key(k) : -1;
+    return i < 0 ? WideInst{nullptr, "", k.kind} : WideInst{table[i], kWideNames[i], k.kind};
 }
-WideInst wide_kernel(const IpmParams& P, int64_t B) { return find_inst(kSolveKeys, kSolveInst, solve_key(P, B)); }
-WideInst wide_pp_kernel(const IpmParams& P, int64_t B) {
-    return find_inst(kPPSolveKeys, kPPSolveInst, pp_solve_key(P, B));
+WideInst wide_kernel(int kind, const IpmParams& P, int64_t B) {
+    return find_inst(kind == PP_SOLVE ? pp_solve_key(P, B) : kind == START ? start_key(P) : solve_key(P, B));
 }
-WideInst wide_start_kernel(const IpmParams& P) { return find_inst(kStartKeys, kStartInst, start_key(P)); }
 
 // XCDs of the current device (HW_REG_XCC_ID partitions of the workspace slots); 8 on an
 // MI355X in SPX mode, fewer on a partitioned device
@@ -133,7 +100,7 @@ static int device_xccs() {
 // A phase's slot budget (wide_plan.h slot_count): four times the wavefronts the device can hold
 // resident at once -- occupancy of the batch instance at its LDS size times the CUs
 static int64_t slot_budget(const IpmParams& P, int64_t B) {
-    const void* fn = wide_kernel(P, B).fn;
+    const void* fn = wide_kernel(SOLVE, P, B).fn;
     const size_t lds = wide_lds_bytes(P);
     int dev = 0, cus = 0, per = 0;
     if (fn && hipGetDevice(&dev) == hipSuccess &&
@@ -189,18 +156,11 @@ static int64_t resume_workers(int64_t B) {
     }();
     return env > 0 ? env : MPCG_RESUME_WORKERS + B / 65536;
 }
-// The problem arrays every phase of a solve shares (n_prob problems: the caller's batch).
-struct WideProblem {
-    const double *state, *coeffs;
-    double *u0, *traj;
-    int32_t* status;
-    double* obj;
-    int32_t *iters, *diag;
-    int64_t n_prob;
-    double* sol = nullptr;  // the solution records [n_prob][solution_elems(N)], or null
-};
-// One batch launch (with its resume workers, drain and overflow launches): the instance inst for
-// parameters P, on B problems in the given order, on the workspace `lay` at base.  handoff: the
+// One batch launch (with its resume workers, drain and overflow launches) of a solve request (its
+// arrays are shared by every phase: rq.B problems, the caller's batch): the instance inst for
+// parameters P, on B problems in the given order, on the workspace `lay` at base.  The kind of
+// inst says what the kernels take after WideArgs -- PP_SOLVE: the request's rows, START: its
+// start as StartIn (which carries the rows) -- and which resume instance continues it.  handoff: the
 // fp32 configuration's hand-over buffer (the fp32 phase writes it, the fp64 phase -- inst a
 // k_warm_wide instance -- reads it).  nworkers: concurrent resume workers (0: resume_workers).
 // origin (the fp32 configuration's head): &the caller's stream (a pointer: the caller's stream may
@@ -220,12 +180,6 @@ struct PhaseLaunch {
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;
     int64_t nworkers = 0;
     const hipStream_t* origin = nullptr;
-    // per-problem parameter rows [n_prob][16] (inst: a k_solve_wide_pp instance; the resume
-    // launches then take the k_resume_wide_pp instance and the same rows), or null
-    const double* pparams = nullptr;
-    // a started solve (inst: a k_start_wide instance; the resume launches take the
-    // k_resume_wide_start instance and the same argument, which carries the rows), or null
-    const StartIn* start = nullptr;
 };
 // the solver addresses its dynamic LDS from address 0 (wave_dev.h): no static LDS
 static hipError_t set_dynamic_lds(const void* fn, size_t lds) {
@@ -241,7 +195,7 @@ static hipError_t join(hipEvent_t ev, hipStream_t from, hipStream_t into) {
     return e != hipSuccess ? e : hipStreamWaitEvent(into, ev, 0);
 }
 // (*forked_out: whether aux received work)
-static hipError_t launch_phase(const WideProblem& pb, const PhaseLaunch& L, bool* forked_out = nullptr) {
+static hipError_t launch_phase(const SolveRequest& rq, const PhaseLaunch& L, bool* forked_out = nullptr) {
     const IpmParams& P = L.P;
     const PhaseLayout& W = *L.lay;
     size_t lds = wide_lds_bytes(P);
@@ -252,10 +206,7 @@ static hipError_t launch_phase(const WideProblem& pb, const PhaseLaunch& L, bool
     const void* fn = L.inst.fn;
     if (!fn) return hipErrorInvalidValue;
     const bool fp32_phase = P.precision == 1 && L.handoff;  // (parks nothing: its endings go to the hand-over)
-    const void* rf = fp32_phase  ? nullptr
-                     : L.start   ? find_inst(kStartResumeKeys, kStartResumeInst, start_resume_key(P)).fn
-                     : L.pparams ? find_inst(kPPResumeKeys, kPPResumeInst, pp_resume_key(P)).fn
-                                 : find_inst(kResumeKeys, kResumeInst, resume_key(P)).fn;
+    const void* rf = fp32_phase ? nullptr : find_inst(resume_key_of(L.inst.kind, P)).fn;
     if (!fp32_phase && !rf) return hipErrorInvalidValue;
     // (every host-side call before the first launch: the device does not wait for the host
     // between the reset kernel and the solver -- ~15 us of a B = 1 solve otherwise)
@@ -264,8 +215,8 @@ static hipError_t launch_phase(const WideProblem& pb, const PhaseLaunch& L, bool
     if (e != hipSuccess) return e;
     const int64_t B = L.B, ns = W.nslots, pc = W.park_cap, nov = W.has_ovf() ? B : 0;
     int32_t* cnt = (int32_t*)(L.base + W.counters.off);
-    WideArgs a{.P = P, .B = B, .order = L.order, .state = pb.state, .coeffs = pb.coeffs, .u0 = pb.u0, .traj = pb.traj,
-               .status = pb.status, .obj = pb.obj, .iters = pb.iters, .diag = pb.diag, .n_prob = pb.n_prob,
+    WideArgs a{.P = P, .B = B, .order = L.order, .state = rq.state, .coeffs = rq.coeffs, .u0 = rq.u0, .traj = rq.traj,
+               .status = rq.status, .obj = rq.obj, .iters = rq.iters, .diag = rq.diag, .n_prob = rq.B,
                .slots = L.base + W.slots.off, .slot_flags = (int32_t*)(L.base + W.flags.off), .nslots = (int32_t)ns,
                .slot_elems = (int32_t)W.slot_elems, .park_count = cnt + PhaseLayout::PARK_COUNT,
                .park_cap = fp32_phase ? 0 : (int32_t)pc, .park_idx = (int64_t*)(L.base + W.park_idx.off),
@@ -274,12 +225,13 @@ static hipError_t launch_phase(const WideProblem& pb, const PhaseLaunch& L, bool
                .started = cnt + PhaseLayout::STARTED, .ovf_count = cnt + PhaseLayout::OVF_COUNT,
                .ovf_taken = cnt + PhaseLayout::OVF_TAKEN, .ovf_idx = (int64_t*)(L.base + W.ovf.off),
                .nxcc = (int32_t)W.nxcc, .phase = 0, .ent0 = 0, .ovf_mark = 2, .handoff = L.handoff,
-               .handoff_stride = L.handoff ? L.handoff_stride : 0, .sol = pb.sol,
+               .handoff_stride = L.handoff ? L.handoff_stride : 0, .sol = rq.sol,
                .sol_stride = solution_elems(P.N)};
-    // (the per-problem kernels take the rows as a second argument, after WideArgs)
-    // (the started solve's kernels take StartIn there instead)
-    const double* rows = L.pparams;
-    void* second = L.start ? (void*)L.start : (void*)&rows;
+    // (the per-problem kernels take the rows as a second argument, after WideArgs; the started
+    // solve's kernels take StartIn there instead; the other kinds read no second argument)
+    const double* rows = rq.rows;
+    const StartIn si{rq.start.rec, solution_elems(P.N), rq.start.mode, rq.start.mu0, rq.start.used, rq.rows};
+    void* second = L.inst.kind == START ? (void*)&si : (void*)&rows;
     void* args[] = {(void*)&a, second};
     // the resume workers: parked problems (the restoration phase) continued by k_resume_wide
     // fork: the resume workers on the aux stream alongside the batch kernel (the fork point is
@@ -342,33 +294,23 @@ static hipError_t launch_phase(const WideProblem& pb, const PhaseLaunch& L, bool
     return hipGetLastError();
 }
 
-hipError_t launch_wide_solve(const IpmParams& P, int64_t B, const double* state, const double* coeffs, double* u0,
-                             double* traj, int32_t* status, double* obj, int32_t* iters, int32_t* diag,
-                             const int32_t* order, void* spill, size_t spill_bytes, hipStream_t stream,
-                             const WideStreams& ws, const char** kernel_name, const double* pparams,
-                             double* sol, const WideStart* start) {
+hipError_t launch_wide_solve(const IpmParams& P, const SolveRequest& pb, const int32_t* order, void* spill,
+                             size_t spill_bytes, hipStream_t stream, const WideStreams& ws,
+                             const char** kernel_name) {
+    const int64_t B = pb.B;
     if (B <= 0) return hipSuccess;
     if (!spill) return hipErrorInvalidValue;
     const SolveLayout W = solve_layout(P, B);
     if (W.total > spill_bytes) return hipErrorInvalidValue;
-    const WideProblem pb{state, coeffs, u0, traj, status, obj, iters, diag, B, sol};
     // (per-problem rows: the same workspace -- the per-problem instance has its plain twin's LDS
     // size and register allocation, so the slot budget is the plain instance's)
-    PhaseLaunch L{.P = P, .inst = start     ? wide_start_kernel(P)
-                                  : pparams ? wide_pp_kernel(P, B)
-                                            : wide_kernel(P, B),
-                  .B = B, .order = order, .lay = &W.first, .base = (char*)spill, .stream = stream, .aux = ws.aux,
-                  .ev_fork = ws.ev_fork, .ev_join = ws.ev_join, .pparams = pparams};
-    if (!L.inst.fn) return hipErrorInvalidValue;
     // (a started solve: the rows travel in StartIn; fp64 only -- start_key)
-    const StartIn si{start ? start->rec : nullptr, solution_elems(P.N), start ? start->mode : nullptr,
-                      start ? start->mu0 : nullptr, start ? start->used : nullptr, pparams};
-    if (start) {
-        if (W.two || !start->rec || !start->mode) return hipErrorInvalidValue;
-        L.start = &si;
-        L.pparams = nullptr;
-    }
-    if (pparams && W.two) return hipErrorInvalidValue;  // (the fp32 configuration: refused, wide_plan.h pp_solve_key)
+    PhaseLaunch L{.P = P, .inst = wide_kernel(pb.started() ? START : pb.rows ? PP_SOLVE : SOLVE, P, B), .B = B,
+                  .order = order, .lay = &W.first, .base = (char*)spill, .stream = stream, .aux = ws.aux,
+                  .ev_fork = ws.ev_fork, .ev_join = ws.ev_join};
+    if (!L.inst.fn) return hipErrorInvalidValue;
+    if (pb.started() && (W.two || !pb.start.rec || !pb.start.mode)) return hipErrorInvalidValue;
+    if (pb.rows && W.two) return hipErrorInvalidValue;  // (the fp32 configuration: refused, wide_plan.h pp_solve_key)
     if (kernel_name) *kernel_name = L.inst.name;
     if (!W.two) return launch_phase(pb, L);
     // the fp32 configuration: [the head on aux, in fp64 from the start] the fp32 phase (hand-over,
@@ -390,7 +332,7 @@ hipError_t launch_wide_solve(const IpmParams& P, int64_t B, const double* state,
         // stream, which a captured graph does not survive -- and both join it after the fp32 phase)
         PhaseLaunch H = L;
         H.P = head_params(P, K);
-        H.inst = wide_kernel(H.P, B);  // (the fp64 solver's batch instance)
+        H.inst = wide_kernel(SOLVE, H.P, B);  // (the fp64 solver's batch instance)
         H.B = K;
         H.lay = &W.head;
         H.base = (char*)spill + W.head_off;
@@ -412,8 +354,8 @@ hipError_t launch_wide_solve(const IpmParams& P, int64_t B, const double* state,
         e = head_workers ? join(ws.ev_join2, ws.aux2, stream) : hipSuccess;
         if (e == hipSuccess) e = join(ws.ev_join, ws.aux, stream);
         if (e != hipSuccess) return e;
-        if (diag) {  // (solved from the start by the fp64 solver: diag[:, 2] = 3, after the head's last write)
-            hipLaunchKernelGGL(k_mark_rows, dim3((unsigned)((K + 255) / 256)), dim3(256), 0, stream, K, order, diag, 3, B);
+        if (pb.diag) {  // (solved from the start by the fp64 solver: diag[:, 2] = 3, after the head's last write)
+            hipLaunchKernelGGL(k_mark_rows, dim3((unsigned)((K + 255) / 256)), dim3(256), 0, stream, K, order, pb.diag, 3, B);
             e = hipGetLastError();
             if (e != hipSuccess) return e;
         }
@@ -430,7 +372,7 @@ hipError_t launch_wide_solve(const IpmParams& P, int64_t B, const double* state,
     // phase early in the launch: more concurrent resume workers than a batch of the fp64 solver
     // needs, so they are continued while the rest of the batch runs)
     L.P = Pr;
-    L.inst = find_inst(kWarmKeys, kWarmInst, warm_key(Pr));
+    L.inst = find_inst(warm_key(Pr));
     L.order = order2;
     L.lay = &lay64;
     L.nworkers = 8 + B / 2048;

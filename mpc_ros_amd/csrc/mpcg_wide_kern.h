@@ -1,8 +1,8 @@
 // mpc_ros_amd/csrc/mpcg_wide_kern.h -- the solver kernels of mpcg_wide.hip (one problem per
 // wavefront, wide_core.h) as templates.  Each instance is compiled in its own translation
-// unit (mpcg_wide_inst.hip, one group per MPCG_INST value, built in parallel; the lists of
-// instances and groups are in wide_plan.h); the dispatcher in mpcg_wide.hip reaches them
-// through solve_kernel_fn / resume_kernel_fn / warm_kernel_fn.
+// unit (mpcg_wide_inst.hip, one group per MPCG_INST value, built in parallel; the list of
+// instances and groups is in wide_plan.h); the dispatcher in mpcg_wide.hip reaches them
+// through wide_group.
 //
 // One workgroup = one wavefront = one problem; the problem's whole state lives in
 // the workgroup's LDS (WideLayout: 19.0 KB at N = 20, i.e. 8 problems resident per
@@ -70,7 +70,7 @@ struct WideArgs {
     double* sol;
     int64_t sol_stride;
 };
-// A solve started from solution records (k_start_wide, k_resume_wide_start; include/mpcg.h
+// A solve started from solution records (k_start_wide, k_resume_wide<START_RESUME>; include/mpcg.h
 // mpcg_solve_device_start): the records [n_prob][stride] (WideSolver::solution_out's layout),
 // the mode of each problem, the barrier parameter of each FULL start (or null: mu_init), the
 // mode that ran (or null), and a parameter row per problem (or null: the handle's parameters).
@@ -506,9 +506,25 @@ __device__ __forceinline__ int64_t take_overflow(const WideArgs& a) {
 
 // (one wavefront per SIMD: the restoration phase and the resumed solve get the whole
 // register file -- the workers are few, and the drain runs after the batch kernel)
-// (k_resume_wide_pp below is this kernel's twin for per-problem parameters: keep the two in step)
-template <int MODEL, bool SPLIT, class T, int NB>
-__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 1))) k_resume_wide(WideArgs a) {
+// One kernel for the three resume kinds (wide_plan.h WideKind), which differ in the parameters
+// and in how an overflow problem starts again; the park / overflow protocol is written once.
+//   RESUME        no further argument; an overflow problem of the fp32 configuration's fp64
+//                 phase continues from its hand-over, any other is solved from the start.
+//   PP_RESUME     in: the parameter rows (const double*).  The same parameters as k_solve_wide_pp
+//                 gave problem p, from row p again (valid: the batch kernel parks or lists only
+//                 problems it solved); fp64, no hand-over.
+//   START_RESUME  in: StartIn.  A parked problem is continued from its park entry, which holds
+//                 the started solve's iterate, row scales and objective scale; an overflow
+//                 problem starts again from its record (unchanged: the batch kernel wrote no
+//                 output of a problem it listed) in its mode, under its row where the launch
+//                 has rows.
+// The kind is a parameter of the kernel and its branches are `if constexpr`: each instance
+// compiles to the code its hand-written copy had.  A body shared through a function (also a
+// __forceinline__ one) called from three thin kernels does not: it changes the instances' code.
+template <int KIND, int MODEL, bool SPLIT, class T, int NB, class... In>
+__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 1))) k_resume_wide(WideArgs a, In... in) {
+    static_assert(KIND == RESUME || KIND == PP_RESUME || KIND == START_RESUME, "a resume kind");
+    static_assert(sizeof...(In) == (KIND == RESUME ? 0 : 1), "PP_RESUME: the rows; START_RESUME: StartIn");
     const int t = threadIdx.x;
     const WideLayout Lw(a.P.N, a.P.filter_cap, MODEL);
     typedef WideSolver<DevWave, MODEL, SPLIT, T, NB, false, false> Solver;  // (RCK: no registers to spare here)
@@ -537,122 +553,38 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 1)))
         for (int j = 0; j < 4; ++j) pr.c[j] = (T)a.coeffs[p * 4 + j];
         DevWave wv;
         wv.t = t;
-        Solver S(a.P, pr, wv, ent + Solver::PARK_SCALARS + Lw.total());
-        if (a.phase == 0) {
-            if (!S.park_entry_ok(ent, p)) index_fault("parked entry's tag / counts: problem", p, a.n_prob);
-            S.unpark(ent);
-        } else {
-            if (a.handoff && a.handoff[p * a.handoff_stride] != 0.0f)
-                S.init_warm(a.handoff + p * a.handoff_stride);  // (the fp32 configuration's fp64 phase)
-            else
-                S.init();
-            S.run();
-        }
-        S.finish_resto();
-        write_out(a, S, p, a.phase == 0 ? 1 : a.ovf_mark);
-    }
-}
-// k_resume_wide with a parameter row per problem (mpcg_solve_device_pp; fp64, no hand-over): the
-// same parameters as k_solve_wide_pp gave problem p, from row p again (valid: the batch kernel
-// parks or lists only problems it solved).  A copy of k_resume_wide's body but for the
-// parameters and the hand-over -- a change to either kernel's protocol belongs in both.  (A
-// body shared through a function does not keep k_resume_wide's instances' code as it is.)
-template <int MODEL, bool SPLIT, class T, int NB>
-__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 1)))
-k_resume_wide_pp(WideArgs a, const double* pparams) {
-    const int t = threadIdx.x;
-    const WideLayout Lw(a.P.N, a.P.filter_cap, MODEL);
-    typedef WideSolver<DevWave, MODEL, SPLIT, T, NB, false, false> Solver;  // (RCK: no registers to spare here)
-    for (;;) {
-        int64_t p;
-        T* ent;
-        if (a.phase == 0) {
-            const int e = take_parked(a);
-            if (e < 0) return;
-            check_index("parked entry", e, a.park_cap);
-            p = a.park_idx[e];
-            check_index("parked problem", p, a.n_prob);
-            ent = (T*)a.park + (int64_t)e * a.park_stride;
-        } else {
-            p = take_overflow(a);
-            if (p < 0) return;
-            check_index("overflow problem", p, a.n_prob);
-            check_index("overflow worker's park entry", (int64_t)a.ent0 + blockIdx.x, a.park_cap);
-            ent = (T*)a.park + (int64_t)(a.ent0 + blockIdx.x) * a.park_stride;
-        }
-        IpmProblem<T> pr;
-#pragma unroll
-        for (int j = 0; j < 6; ++j) pr.init[j] = (T)a.state[p * 6 + j];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) pr.c[j] = (T)a.coeffs[p * 4 + j];
-        DevWave wv;
-        wv.t = t;
         IpmParams Pk = a.P;
-        const PPRow row = pp_load_row(pparams, p);
-        pp_row_apply(row.f, Pk);
-        Solver S(Pk, pr, wv, ent + Solver::PARK_SCALARS + Lw.total());
-        if (a.phase == 0) {
-            if (!S.park_entry_ok(ent, p)) index_fault("parked entry's tag / counts: problem", p, a.n_prob);
-            S.unpark(ent);
-        } else {
-            S.init();
-            S.run();
-        }
-        S.finish_resto();
-        write_out(a, S, p, a.phase == 0 ? 1 : a.ovf_mark);
-    }
-}
-
-// k_resume_wide for a started solve (mpcg_solve_device_start; fp64, no hand-over): a parked problem
-// is continued from its park entry, which holds the started solve's iterate, row scales and
-// objective scale; an overflow problem starts again from its record (unchanged: the batch kernel
-// wrote no output of a problem it listed) in its mode, under its parameter row where the launch
-// has rows.  A copy of k_resume_wide_pp's body but for that -- a change to the protocol belongs
-// in all three.
-template <int MODEL, bool SPLIT, class T, int NB>
-__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 1)))
-k_resume_wide_start(WideArgs a, StartIn sa) {
-    const int t = threadIdx.x;
-    const WideLayout Lw(a.P.N, a.P.filter_cap, MODEL);
-    typedef WideSolver<DevWave, MODEL, SPLIT, T, NB, false, false> Solver;  // (RCK: no registers to spare here)
-    for (;;) {
-        int64_t p;
-        T* ent;
-        if (a.phase == 0) {
-            const int e = take_parked(a);
-            if (e < 0) return;
-            check_index("parked entry", e, a.park_cap);
-            p = a.park_idx[e];
-            check_index("parked problem", p, a.n_prob);
-            ent = (T*)a.park + (int64_t)e * a.park_stride;
-        } else {
-            p = take_overflow(a);
-            if (p < 0) return;
-            check_index("overflow problem", p, a.n_prob);
-            check_index("overflow worker's park entry", (int64_t)a.ent0 + blockIdx.x, a.park_cap);
-            ent = (T*)a.park + (int64_t)(a.ent0 + blockIdx.x) * a.park_stride;
-        }
-        IpmProblem<T> pr;
-#pragma unroll
-        for (int j = 0; j < 6; ++j) pr.init[j] = (T)a.state[p * 6 + j];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) pr.c[j] = (T)a.coeffs[p * 4 + j];
-        DevWave wv;
-        wv.t = t;
-        IpmParams Pk = a.P;
-        if (sa.pparams) {
-            const PPRow row = pp_load_row(sa.pparams, p);
+        if constexpr (KIND == PP_RESUME) {
+            const double* rows = (in, ...);
+            const PPRow row = pp_load_row(rows, p);
             pp_row_apply(row.f, Pk);
         }
+        if constexpr (KIND == START_RESUME) {
+            const StartIn& sa = (in, ...);
+            if (sa.pparams) {
+                const PPRow row = pp_load_row(sa.pparams, p);
+                pp_row_apply(row.f, Pk);
+            }
+        }
         Solver S(Pk, pr, wv, ent + Solver::PARK_SCALARS + Lw.total());
         if (a.phase == 0) {
             if (!S.park_entry_ok(ent, p)) index_fault("parked entry's tag / counts: problem", p, a.n_prob);
             S.unpark(ent);
         } else {
-            const int md = __builtin_amdgcn_readfirstlane(sa.mode[p]);
-            const double m0 = sa.mu0 ? sa.mu0[p] : Pk.mu_init;
-            const int used = S.init_start(sa.start + p * sa.stride, md, (T)m0);
-            if (sa.used && t == 0) sa.used[p] = used;
+            if constexpr (KIND == START_RESUME) {
+                const StartIn& sa = (in, ...);
+                const int md = __builtin_amdgcn_readfirstlane(sa.mode[p]);
+                const double m0 = sa.mu0 ? sa.mu0[p] : Pk.mu_init;
+                const int used = S.init_start(sa.start + p * sa.stride, md, (T)m0);
+                if (sa.used && t == 0) sa.used[p] = used;
+            } else if constexpr (KIND == PP_RESUME) {
+                S.init();
+            } else {
+                if (a.handoff && a.handoff[p * a.handoff_stride] != 0.0f)
+                    S.init_warm(a.handoff + p * a.handoff_stride);  // (the fp32 configuration's fp64 phase)
+                else
+                    S.init();
+            }
             S.run();
         }
         S.finish_resto();
@@ -660,56 +592,20 @@ k_resume_wide_start(WideArgs a, StartIn sa) {
     }
 }
 
-// Kernel instances (host stubs), defined in mpcg_wide_inst.hip: the instance of
-// k_solve_wide<MODEL, SPLIT, T, NB, DEFOPT, WPE> / k_resume_wide<MODEL, SPLIT, T, NB>.
-template <int MODEL, bool SPLIT, class T, int NB, bool DEFOPT, int WPE>
-const void* solve_kernel_fn();
-// (the dispatcher's choice, mpcg_wide.hip: the instance of a key -- wide_plan.h solve_key /
-// resume_key / warm_key -- and its name, "k_solve_wide<M,S,T,NB,D,W>"; fn null: not in the library)
+// The instances the library carries are the rows of wide_plan.h's MPCG_WIDE_INSTANCES, each
+// compiled in its group's translation unit: wide_group<G> (mpcg_wide_inst.hip, compiled with
+// -DMPCG_INST=G) writes the kernel of every row of group G into t[the row's index].
+template <int G>
+void wide_group(const void** t);
+// (the dispatcher's choice, mpcg_wide.hip: the batch instance of a kind -- SOLVE, PP_SOLVE or
+// START; wide_plan.h solve_key / pp_solve_key / start_key -- and its name,
+// "k_solve_wide<M,S,T,NB,D,W>"; fn null: refused parameters, or not in the library)
 struct WideInst {
     const void* fn;
     const char* name;
+    int kind;
 };
-WideInst wide_kernel(const IpmParams& P, int64_t B);
-template <int MODEL, bool SPLIT, class T, int NB>
-const void* resume_kernel_fn();
-template <int MODEL, bool SPLIT, class T, int NB, bool DEFOPT, int WPE>
-const void* warm_kernel_fn();
-// (the per-problem instances, k_solve_wide_pp / k_resume_wide_pp: wide_plan.h pp_solve_key / pp_resume_key)
-template <int MODEL, bool SPLIT, class T, int NB, bool DEFOPT, int WPE>
-const void* pp_solve_kernel_fn();
-template <int MODEL, bool SPLIT, class T, int NB>
-const void* pp_resume_kernel_fn();
-WideInst wide_pp_kernel(const IpmParams& P, int64_t B);
-// (the started solve's instances, k_start_wide / k_resume_wide_start: wide_plan.h start_key / start_resume_key)
-template <int MODEL, bool SPLIT, class T, int NB, bool DEFOPT, int WPE>
-const void* start_kernel_fn();
-template <int MODEL, bool SPLIT, class T, int NB>
-const void* start_resume_kernel_fn();
-WideInst wide_start_kernel(const IpmParams& P);
-
-// (the instances the library carries: the lists of wide_plan.h)
-#define MPCG_DECL_SOLVE(g, M, S, T, NB, D, W) template <> const void* solve_kernel_fn<M, S, T, NB, D, W>();
-#define MPCG_DECL_WARM(g, M, S, T, NB, D, W) template <> const void* warm_kernel_fn<M, S, T, NB, D, W>();
-#define MPCG_DECL_RESUME(g, M, S, T, NB) template <> const void* resume_kernel_fn<M, S, T, NB>();
-MPCG_WIDE_SOLVE_INSTANCES(MPCG_DECL_SOLVE)
-MPCG_WIDE_RESUME_INSTANCES(MPCG_DECL_RESUME)
-MPCG_WIDE_WARM_INSTANCES(MPCG_DECL_WARM)
-#define MPCG_DECL_PP_SOLVE(g, M, S, T, NB, D, W) template <> const void* pp_solve_kernel_fn<M, S, T, NB, D, W>();
-#define MPCG_DECL_PP_RESUME(g, M, S, T, NB) template <> const void* pp_resume_kernel_fn<M, S, T, NB>();
-MPCG_WIDE_PP_SOLVE_INSTANCES(MPCG_DECL_PP_SOLVE)
-MPCG_WIDE_PP_RESUME_INSTANCES(MPCG_DECL_PP_RESUME)
-#define MPCG_DECL_START(g, M, S, T, NB, D, W) template <> const void* start_kernel_fn<M, S, T, NB, D, W>();
-#define MPCG_DECL_START_RESUME(g, M, S, T, NB) template <> const void* start_resume_kernel_fn<M, S, T, NB>();
-MPCG_WIDE_START_INSTANCES(MPCG_DECL_START)
-MPCG_WIDE_START_RESUME_INSTANCES(MPCG_DECL_START_RESUME)
-#undef MPCG_DECL_START
-#undef MPCG_DECL_START_RESUME
-#undef MPCG_DECL_PP_SOLVE
-#undef MPCG_DECL_PP_RESUME
-#undef MPCG_DECL_SOLVE
-#undef MPCG_DECL_WARM
-#undef MPCG_DECL_RESUME
+WideInst wide_kernel(int kind, const IpmParams& P, int64_t B);
 
 }  // namespace mpcg
 #endif

@@ -1,7 +1,7 @@
 // mpc_ros_amd/csrc/wide_plan.h -- the launch plan of the wavefront solver (mpcg_wide.hip), as
 // plain arithmetic on (IpmParams, B, slot budget, XCD count): the kernel instances the library
 // carries and the choice among them, the layout of the HBM workspace, and the layout of a control
-// tick's scratch (TickLayout: plain arithmetic on (B, Mmax, rows)).  No GPU runtime: the
+// tick's scratch and of a host solve's staging (TickLayout, IoLayout).  No GPU runtime: the
 // launch side passes in what only the runtime can say (the occupancy behind the slot budget,
 // the XCD count), and tests/native/wide_plan_check.cpp checks all of it on the host.
 #ifndef MPCG_WIDE_PLAN_H
@@ -14,92 +14,98 @@
 
 #include "wide_core.h"
 
-// (group, model, split, type, blocks, default options, waves per SIMD): the instances the
-// library carries; group = the MPCG_INST translation unit that compiles it
-#define MPCG_WIDE_SOLVE_INSTANCES(X)          \
-    X(0, 0, true, double, 1, true, 2)         \
-    X(0, 0, true, double, 1, true, 1)         \
-    X(1, 0, true, double, 1, false, 2)        \
-    X(2, 0, false, double, 1, false, 2)       \
-    X(2, 0, false, double, 1, false, 1)       \
-    X(5, 0, false, double, 1, true, 2)        \
-    X(3, 0, false, double, 2, false, 1)       \
-    X(1, 0, false, double, 2, true, 1)        \
-    X(6, 0, false, double, 1, true, 1)        \
-    X(4, 0, true, float, 1, false, 3)         \
-    X(5, 0, false, float, 1, false, 3)        \
-    X(6, 0, false, float, 2, false, 2)        \
-    X(7, 1, true, double, 1, false, 2)        \
-    X(4, 1, true, double, 1, true, 2)         \
-    X(8, 1, false, double, 1, false, 2)       \
-    X(7, 1, false, double, 1, true, 2)        \
-    X(8, 1, false, double, 1, false, 1)       \
-    X(9, 1, false, double, 2, false, 1)
-// (the fp32 solver's problems that need the restoration phase are solved again in fp64: its
-// resume kernel is the fp64 instance of the same horizon)
-#define MPCG_WIDE_RESUME_INSTANCES(X)         \
-    X(1, 0, true, double, 1)                  \
-    X(2, 0, false, double, 1)                 \
-    X(3, 0, false, double, 2)                 \
-    X(7, 1, true, double, 1)                  \
-    X(8, 1, false, double, 1)                 \
-    X(9, 1, false, double, 2)
-// the fp64 phase of the fp32 configuration (k_warm_wide), default options: per horizon class
-#define MPCG_WIDE_WARM_INSTANCES(X)           \
-    X(10, 0, true, double, 1, true, 2)        \
-    X(10, 0, false, double, 1, true, 2)       \
-    X(11, 0, false, double, 1, true, 1)       \
-    X(11, 0, false, double, 2, true, 1)
-// Per-problem parameter rows (include/mpcg.h MPCG_PP_*; mpcg_solve_device_pp): the batch kernel
-// k_solve_wide_pp, general options, fp64, one per (model, horizon class) -- and the
-// default-options instance of the benchmark class -- and its resume kernels k_resume_wide_pp:
-// lists and groups of their own (the lists above are what solve_key / resume_key choose from)
-#define MPCG_WIDE_PP_SOLVE_INSTANCES(X)       \
-    X(12, 0, true, double, 1, false, 2)       \
-    X(19, 0, true, double, 1, true, 2)        \
-    X(13, 0, false, double, 1, false, 2)      \
-    X(14, 0, false, double, 1, false, 1)      \
-    X(14, 0, false, double, 2, false, 1)      \
-    X(15, 1, true, double, 1, false, 2)       \
-    X(16, 1, false, double, 1, false, 2)      \
-    X(17, 1, false, double, 1, false, 1)      \
-    X(18, 1, false, double, 2, false, 1)
-#define MPCG_WIDE_PP_RESUME_INSTANCES(X)      \
-    X(12, 0, true, double, 1)                 \
-    X(13, 0, false, double, 1)                \
-    X(15, 0, false, double, 2)                \
-    X(16, 1, true, double, 1)                 \
-    X(17, 1, false, double, 1)                \
-    X(18, 1, false, double, 2)
-// A solve started from a solution record (include/mpcg.h mpcg_solve_device_start): the batch
-// kernel k_start_wide, general options, fp64, one per (model, horizon class) -- a parameter row
-// per problem or none is a run-time argument of the one instance -- and its resume kernels
-// k_resume_wide_start, whose overflow re-solve starts from the record again: lists and groups
-// of their own
-#define MPCG_WIDE_START_INSTANCES(X)          \
-    X(20, 0, true, double, 1, false, 2)       \
-    X(21, 0, false, double, 1, false, 2)      \
-    X(22, 0, false, double, 1, false, 1)      \
-    X(23, 0, false, double, 2, false, 1)      \
-    X(24, 1, true, double, 1, false, 2)       \
-    X(25, 1, false, double, 1, false, 2)      \
-    X(26, 1, false, double, 1, false, 1)      \
-    X(27, 1, false, double, 2, false, 1)
-#define MPCG_WIDE_START_RESUME_INSTANCES(X)   \
-    X(28, 0, true, double, 1)                 \
-    X(29, 0, false, double, 1)                \
-    X(30, 0, false, double, 2)                \
-    X(31, 1, true, double, 1)                 \
-    X(32, 1, false, double, 1)                \
-    X(33, 1, false, double, 2)
-// (an instance's name: mpcg_last_kernel() reports the one a solve launched)
-#define MPCG_SOLVE_NAME(M, S, T, NB, D, W) "k_solve_wide<" #M "," #S "," #T "," #NB "," #D "," #W ">"
-#define MPCG_WARM_NAME(M, S, T, NB, D, W) "k_warm_wide<" #M "," #S "," #T "," #NB "," #D "," #W ">"
-#define MPCG_RESUME_NAME(M, S, T, NB) "k_resume_wide<" #M "," #S "," #T "," #NB ">"
-#define MPCG_PP_SOLVE_NAME(M, S, T, NB, D, W) "k_solve_wide_pp<" #M "," #S "," #T "," #NB "," #D "," #W ">"
-#define MPCG_PP_RESUME_NAME(M, S, T, NB) "k_resume_wide_pp<" #M "," #S "," #T "," #NB ">"
-#define MPCG_START_NAME(M, S, T, NB, D, W) "k_start_wide<" #M "," #S "," #T "," #NB "," #D "," #W ">"
-#define MPCG_START_RESUME_NAME(M, S, T, NB) "k_resume_wide_start<" #M "," #S "," #T "," #NB ">"
+// The instances the library carries, one row each:
+//   X(group, kind, model, split, type, blocks, default options, waves per SIMD)
+// group: the MPCG_INST translation unit that compiles it (mpcg_wide_inst.hip); kind: a WideKind
+// below -- which kernel, and which key function chooses among the rows of the kind.  A resume row
+// carries no options and no allocation of its own (false, 0: k_resume_wide reads the options and
+// is always allocated for one wavefront per SIMD).
+//   SOLVE         k_solve_wide (solve_key).
+//   RESUME        k_resume_wide<RESUME> (resume_key).  The fp32 solver's problems that need the
+//                 restoration phase are solved again in fp64: its resume kernel is the fp64
+//                 instance of the same horizon.
+//   WARM          k_warm_wide, the fp64 phase of the fp32 configuration, default options: per
+//                 horizon class (warm_key).
+//   PP_SOLVE      k_solve_wide_pp, a parameter row per problem (include/mpcg.h MPCG_PP_*;
+//                 mpcg_solve_device_pp): general options, fp64, one per (model, horizon class)
+//                 -- and the default-options instance of the benchmark class (pp_solve_key).
+//   PP_RESUME     k_resume_wide<PP_RESUME> (pp_resume_key).
+//   START         k_start_wide, a solve started from a solution record (include/mpcg.h
+//                 mpcg_solve_device_start): general options, fp64, one per (model, horizon class)
+//                 -- a parameter row per problem or none is a run-time argument of the one
+//                 instance (start_key).
+//   START_RESUME  k_resume_wide<START_RESUME>, whose overflow re-solve starts from the record
+//                 again (start_resume_key).
+// A new kind: an enumerator, its rows (in groups of their own), its kernel (or its branch of
+// k_resume_wide) with the kernel's line in mpcg_wide_inst.hip, its name below, its key function.
+#define MPCG_WIDE_INSTANCES(X)                        \
+    X(0, SOLVE, 0, true, double, 1, true, 2)          \
+    X(0, SOLVE, 0, true, double, 1, true, 1)          \
+    X(1, SOLVE, 0, true, double, 1, false, 2)         \
+    X(2, SOLVE, 0, false, double, 1, false, 2)        \
+    X(2, SOLVE, 0, false, double, 1, false, 1)        \
+    X(5, SOLVE, 0, false, double, 1, true, 2)         \
+    X(3, SOLVE, 0, false, double, 2, false, 1)        \
+    X(1, SOLVE, 0, false, double, 2, true, 1)         \
+    X(6, SOLVE, 0, false, double, 1, true, 1)         \
+    X(4, SOLVE, 0, true, float, 1, false, 3)          \
+    X(5, SOLVE, 0, false, float, 1, false, 3)         \
+    X(6, SOLVE, 0, false, float, 2, false, 2)         \
+    X(7, SOLVE, 1, true, double, 1, false, 2)         \
+    X(4, SOLVE, 1, true, double, 1, true, 2)          \
+    X(8, SOLVE, 1, false, double, 1, false, 2)        \
+    X(7, SOLVE, 1, false, double, 1, true, 2)         \
+    X(8, SOLVE, 1, false, double, 1, false, 1)        \
+    X(9, SOLVE, 1, false, double, 2, false, 1)        \
+    X(1, RESUME, 0, true, double, 1, false, 0)        \
+    X(2, RESUME, 0, false, double, 1, false, 0)       \
+    X(3, RESUME, 0, false, double, 2, false, 0)       \
+    X(7, RESUME, 1, true, double, 1, false, 0)        \
+    X(8, RESUME, 1, false, double, 1, false, 0)       \
+    X(9, RESUME, 1, false, double, 2, false, 0)       \
+    X(10, WARM, 0, true, double, 1, true, 2)          \
+    X(10, WARM, 0, false, double, 1, true, 2)         \
+    X(11, WARM, 0, false, double, 1, true, 1)         \
+    X(11, WARM, 0, false, double, 2, true, 1)         \
+    X(12, PP_SOLVE, 0, true, double, 1, false, 2)     \
+    X(19, PP_SOLVE, 0, true, double, 1, true, 2)      \
+    X(13, PP_SOLVE, 0, false, double, 1, false, 2)    \
+    X(14, PP_SOLVE, 0, false, double, 1, false, 1)    \
+    X(14, PP_SOLVE, 0, false, double, 2, false, 1)    \
+    X(15, PP_SOLVE, 1, true, double, 1, false, 2)     \
+    X(16, PP_SOLVE, 1, false, double, 1, false, 2)    \
+    X(17, PP_SOLVE, 1, false, double, 1, false, 1)    \
+    X(18, PP_SOLVE, 1, false, double, 2, false, 1)    \
+    X(12, PP_RESUME, 0, true, double, 1, false, 0)    \
+    X(13, PP_RESUME, 0, false, double, 1, false, 0)   \
+    X(15, PP_RESUME, 0, false, double, 2, false, 0)   \
+    X(16, PP_RESUME, 1, true, double, 1, false, 0)    \
+    X(17, PP_RESUME, 1, false, double, 1, false, 0)   \
+    X(18, PP_RESUME, 1, false, double, 2, false, 0)   \
+    X(20, START, 0, true, double, 1, false, 2)        \
+    X(21, START, 0, false, double, 1, false, 2)       \
+    X(22, START, 0, false, double, 1, false, 1)       \
+    X(23, START, 0, false, double, 2, false, 1)       \
+    X(24, START, 1, true, double, 1, false, 2)        \
+    X(25, START, 1, false, double, 1, false, 2)       \
+    X(26, START, 1, false, double, 1, false, 1)       \
+    X(27, START, 1, false, double, 2, false, 1)       \
+    X(28, START_RESUME, 0, true, double, 1, false, 0) \
+    X(29, START_RESUME, 0, false, double, 1, false, 0) \
+    X(30, START_RESUME, 0, false, double, 2, false, 0) \
+    X(31, START_RESUME, 1, true, double, 1, false, 0) \
+    X(32, START_RESUME, 1, false, double, 1, false, 0) \
+    X(33, START_RESUME, 1, false, double, 2, false, 0)
+// (an instance's name: mpcg_last_kernel() reports the batch kernel a solve launched)
+#define MPCG_NAME6(k, M, S, T, NB, D, W) k "<" #M "," #S "," #T "," #NB "," #D "," #W ">"
+#define MPCG_NAME4(k, M, S, T, NB, D, W) k #M "," #S "," #T "," #NB ">"
+#define MPCG_NAME_SOLVE(...) MPCG_NAME6("k_solve_wide", __VA_ARGS__)
+#define MPCG_NAME_WARM(...) MPCG_NAME6("k_warm_wide", __VA_ARGS__)
+#define MPCG_NAME_PP_SOLVE(...) MPCG_NAME6("k_solve_wide_pp", __VA_ARGS__)
+#define MPCG_NAME_START(...) MPCG_NAME6("k_start_wide", __VA_ARGS__)
+#define MPCG_NAME_RESUME(...) MPCG_NAME4("k_resume_wide<RESUME,", __VA_ARGS__)
+#define MPCG_NAME_PP_RESUME(...) MPCG_NAME4("k_resume_wide<PP_RESUME,", __VA_ARGS__)
+#define MPCG_NAME_START_RESUME(...) MPCG_NAME4("k_resume_wide<START_RESUME,", __VA_ARGS__)
 
 namespace mpcg {
 
@@ -115,35 +121,43 @@ inline size_t wide_lds_bytes(const IpmParams& P) {
 }
 
 // ---------------------------------------------------------------- the instances and the choice
-// An instance's template arguments (a resume instance: model, split, blocks; the rest zero).
-// model < 0: none -- the parameters are refused.
+enum WideKind { SOLVE, RESUME, WARM, PP_SOLVE, PP_RESUME, START, START_RESUME };
+// An instance's kind and template arguments (a resume instance: model, split, blocks; the rest
+// zero).  model < 0: none -- the parameters are refused.
 struct WideKey {
-    int model = -1;
+    int kind = SOLVE, model = -1;
     bool split = false, f32 = false;
     int nb = 0;
     bool defopt = false;
     int wpe = 0;
     bool ok() const { return model >= 0; }
     bool operator==(const WideKey& o) const {
-        return model == o.model && split == o.split && f32 == o.f32 && nb == o.nb && defopt == o.defopt && wpe == o.wpe;
+        return kind == o.kind && model == o.model && split == o.split && f32 == o.f32 && nb == o.nb &&
+               defopt == o.defopt && wpe == o.wpe;
     }
 };
-#define MPCG_KEY7(g, M, S, T, NB, D, W) WideKey{M, S, sizeof(T) == 4, NB, D, W},
-#define MPCG_KEY5(g, M, S, T, NB) WideKey{M, S, sizeof(T) == 4, NB, false, 0},
-inline constexpr WideKey kSolveKeys[] = {MPCG_WIDE_SOLVE_INSTANCES(MPCG_KEY7)};
-inline constexpr WideKey kResumeKeys[] = {MPCG_WIDE_RESUME_INSTANCES(MPCG_KEY5)};
-inline constexpr WideKey kWarmKeys[] = {MPCG_WIDE_WARM_INSTANCES(MPCG_KEY7)};
-inline constexpr WideKey kPPSolveKeys[] = {MPCG_WIDE_PP_SOLVE_INSTANCES(MPCG_KEY7)};
-inline constexpr WideKey kPPResumeKeys[] = {MPCG_WIDE_PP_RESUME_INSTANCES(MPCG_KEY5)};
-inline constexpr WideKey kStartKeys[] = {MPCG_WIDE_START_INSTANCES(MPCG_KEY7)};
-inline constexpr WideKey kStartResumeKeys[] = {MPCG_WIDE_START_RESUME_INSTANCES(MPCG_KEY5)};
-#undef MPCG_KEY7
-#undef MPCG_KEY5
-template <size_t n>
-inline bool has_key(const WideKey (&keys)[n], const WideKey& k) {
-    for (const WideKey& e : keys)
-        if (e == k) return true;
-    return false;
+// the list as keys, names and groups, row by row (host side: the device code names no instance)
+#define MPCG_ROW_KEY(g, K, M, S, T, NB, D, W) WideKey{K, M, S, sizeof(T) == 4, NB, D, W},
+#define MPCG_ROW_NAME(g, K, M, S, T, NB, D, W) MPCG_NAME_##K(M, S, T, NB, D, W),
+#define MPCG_ROW_GROUP(g, K, M, S, T, NB, D, W) g,
+inline constexpr WideKey kWideKeys[] = {MPCG_WIDE_INSTANCES(MPCG_ROW_KEY)};
+inline constexpr const char* kWideNames[] = {MPCG_WIDE_INSTANCES(MPCG_ROW_NAME)};
+inline constexpr int kWideGroupOf[] = {MPCG_WIDE_INSTANCES(MPCG_ROW_GROUP)};
+#undef MPCG_ROW_KEY
+#undef MPCG_ROW_NAME
+#undef MPCG_ROW_GROUP
+constexpr int kWideInstances = (int)(sizeof(kWideKeys) / sizeof(kWideKeys[0]));
+// the translation units of mpcg_wide_inst.hip: groups 0 .. kWideGroups - 1 (build.py N_INST)
+constexpr int kWideGroups = [] {
+    int n = 0;
+    for (int g : kWideGroupOf) n = g + 1 > n ? g + 1 : n;
+    return n;
+}();
+// the row of a key, -1: the library carries no such instance
+inline int find_key(const WideKey& k) {
+    for (int i = 0; i < kWideInstances; ++i)
+        if (kWideKeys[i] == k) return i;
+    return -1;
 }
 
 // The horizon class of a problem: SPLIT (N <= 32: the recursions use both half-waves), NB stage
@@ -176,7 +190,7 @@ constexpr int64_t kLoneBatch = 4096;
 inline WideKey solve_key(const IpmParams& P, int64_t B) {
     const WideClass c = wide_class(P);
     if (!c.ok) return WideKey{};
-    WideKey k{c.model, c.split, P.precision == 1, c.nb, false, 2};
+    WideKey k{SOLVE, c.model, c.split, P.precision == 1, c.nb, false, 2};
     if (k.f32) {  // (no default-options instance; N <= 64: 3 wavefronts per SIMD, mpcg_wide_kern.h)
         k.wpe = c.nb == 1 ? 3 : 2;
         return k;
@@ -188,16 +202,16 @@ inline WideKey solve_key(const IpmParams& P, int64_t B) {
     const bool bench = c.model == 0 && c.split && k.defopt;  // (the benchmark configuration)
     if (c.one || (bench && B <= kLoneBatch)) k.wpe = 1;
     // (no default-options instance -- the bicycle at one wavefront per SIMD: the general one)
-    if (k.defopt && !has_key(kSolveKeys, k)) k.defopt = false;
+    if (k.defopt && find_key(k) < 0) k.defopt = false;
     return k;
 }
 // the resume kernel of a solve kernel's instance (the general-options instance also for the
 // default-options one: the two compute bitwise the same); for the fp32 solver the fp64
 // instance of the same horizon (a precision-1 launch parks nothing -- the fp32 phase hands every
 // ending to the fp64 phase, no_restoration = 1 keeps it -- so its workers find nothing and exit)
-inline WideKey resume_key(const IpmParams& P) {
+inline WideKey resume_key(const IpmParams& P, WideKind kind = RESUME) {
     const WideClass c = wide_class(P);
-    return c.ok ? WideKey{c.model, c.split, false, c.nb, false, 0} : WideKey{};
+    return c.ok ? WideKey{kind, c.model, c.split, false, c.nb, false, 0} : WideKey{};
 }
 // Per-problem parameter rows: the general-options fp64 instance of the horizon class (the rows
 // fix neither the class nor the LDS layout: N, the model and filter_cap are P's), or the
@@ -206,25 +220,31 @@ inline WideKey resume_key(const IpmParams& P) {
 inline WideKey pp_solve_key(const IpmParams& P, int64_t /*B*/) {
     const WideClass c = wide_class(P);
     if (!c.ok || P.precision != 0) return WideKey{};
-    WideKey k{c.model, c.split, false, c.nb, ipopt_options_are_default(P), c.one ? 1 : 2};
-    if (k.defopt && !has_key(kPPSolveKeys, k)) k.defopt = false;
+    WideKey k{PP_SOLVE, c.model, c.split, false, c.nb, ipopt_options_are_default(P), c.one ? 1 : 2};
+    if (k.defopt && find_key(k) < 0) k.defopt = false;
     return k;
 }
-inline WideKey pp_resume_key(const IpmParams& P) { return P.precision == 0 ? resume_key(P) : WideKey{}; }
+inline WideKey pp_resume_key(const IpmParams& P) { return P.precision == 0 ? resume_key(P, PP_RESUME) : WideKey{}; }
 // A solve started from a record: the general-options fp64 instance of the horizon class (with or
 // without parameter rows), its resume kernel by the class as well; the fp32 configuration is
 // refused
 inline WideKey start_key(const IpmParams& P) {
     const WideClass c = wide_class(P);
     if (!c.ok || P.precision != 0) return WideKey{};
-    return WideKey{c.model, c.split, false, c.nb, false, c.one ? 1 : 2};
+    return WideKey{START, c.model, c.split, false, c.nb, false, c.one ? 1 : 2};
 }
-inline WideKey start_resume_key(const IpmParams& P) { return P.precision == 0 ? resume_key(P) : WideKey{}; }
+inline WideKey start_resume_key(const IpmParams& P) {
+    return P.precision == 0 ? resume_key(P, START_RESUME) : WideKey{};
+}
+// the resume instance that continues what a batch kernel of kind `batch` parks or lists
+inline WideKey resume_key_of(int batch, const IpmParams& P) {
+    return batch == PP_SOLVE ? pp_resume_key(P) : batch == START ? start_resume_key(P) : resume_key(P);
+}
 // the fp64 phase's instance (k_warm_wide, default options) for the horizon class of the fp64
 // parameters Pr (fp64_params): the differential drive only
 inline WideKey warm_key(const IpmParams& Pr) {
     const WideClass c = wide_class(Pr);
-    return c.ok && Pr.model == 0 ? WideKey{0, c.split, false, c.nb, true, c.one ? 1 : 2} : WideKey{};
+    return c.ok && Pr.model == 0 ? WideKey{WARM, 0, c.split, false, c.nb, true, c.one ? 1 : 2} : WideKey{};
 }
 
 // ---------------------------------------------------------------- the two-phase configuration
@@ -391,6 +411,38 @@ struct TickLayout {
         plan = take(sizeof(double) * 2 * (size_t)Mmax * roll);
         count = take(sizeof(int32_t) * roll);
         start = take(sizeof(int32_t) * roll);
+    }
+};
+
+// ---------------------------------------------------------------- the host solve's staging
+// The device copies of a host solve's arrays (mpcg_api.cpp solve_host), one handle buffer: state
+// [B][6] | coeffs [B][4] | u0 [B][2] | traj [B][3][N] | obj [B] | mu0 [B] (a start) | the records
+// [B][solution_elems(N)] (a start, the solution out, or both: solved in place) | the parameter rows
+// [B][16] (rows) | then int32: status [B] | iters [B] | diag [B][4] | mode [B] | used [B] (a start).
+// Every region from an 8-byte boundary, as TickLayout's.
+struct IoLayout {
+    Region state, coeffs, u0, traj, obj, mu0, rec, rows, status, iters, diag, mode, used;
+    size_t total = 0;
+    IoLayout(int64_t B, int N, bool rows_, bool sol, bool start) {
+        const size_t b = (size_t)B, st = start ? b : 0;
+        auto take = [this](size_t bytes) {
+            const Region r{total, round_up(bytes, 8)};
+            total += r.bytes;
+            return r;
+        };
+        state = take(sizeof(double) * 6 * b);
+        coeffs = take(sizeof(double) * 4 * b);
+        u0 = take(sizeof(double) * 2 * b);
+        traj = take(sizeof(double) * 3 * (size_t)N * b);
+        obj = take(sizeof(double) * b);
+        mu0 = take(sizeof(double) * st);
+        rec = take(sol || start ? sizeof(double) * (size_t)solution_elems(N) * b : 0);
+        rows = take(rows_ ? sizeof(double) * kRowFields * b : 0);
+        status = take(sizeof(int32_t) * b);
+        iters = take(sizeof(int32_t) * b);
+        diag = take(sizeof(int32_t) * 4 * b);
+        mode = take(sizeof(int32_t) * st);
+        used = take(sizeof(int32_t) * st);
     }
 };
 

@@ -1,11 +1,14 @@
 // tests/native/wide_plan_check.cpp -- the launch plan of the wavefront solver
-// (mpc_ros_amd/csrc/wide_plan.h: instance choice, workspace layout, tick scratch layout) on the host; no GPU
-// runtime.  Checks the properties below (exit status 1 and a message at the first that fails),
-// then prints the chosen solve instance over the whole input space as JSON, run-length encoded
-// over the horizon: {"model<m>_precision<p>_<default|option>_B<B>": [[N from, N to, name], ...]}
-// ("": refused) -- tests/test_host_logic.py compares it with tests/golden/launch_plan.json.
+// (mpc_ros_amd/csrc/wide_plan.h: the choice among the instances of every kind, workspace layout,
+// tick scratch layout, the host solve's staging layout) on the host; no GPU runtime.  Checks the
+// properties below (exit status 1 and a message at the first that fails), and prints the chosen
+// solve instance over the whole input space as JSON, run-length encoded over the horizon:
+// {"model<m>_precision<p>_<default|option>_B<B>": [[N from, N to, name], ...]} ("": refused) --
+// tests/test_host_logic.py compares it with tests/golden/launch_plan.json.  With the argument
+// "pp" it prints the per-problem solve instance chosen under a non-default option per (model,
+// horizon range) instead (tests/test_pparams_host.py).
 //
-//   g++ -std=c++20 -o wide_plan_check tests/native/wide_plan_check.cpp && ./wide_plan_check
+//   g++ -std=c++20 -o wide_plan_check tests/native/wide_plan_check.cpp && ./wide_plan_check [pp]
 #include <cstdio>
 #include <cstdlib>
 #include <string>
@@ -25,16 +28,6 @@ using namespace mpcg;
         }                                                  \
     } while (0)
 
-#define NAME7(g, M, S, T, NB, D, W) MPCG_SOLVE_NAME(M, S, T, NB, D, W),
-static const char* const kSolveNames[] = {MPCG_WIDE_SOLVE_INSTANCES(NAME7)};
-
-template <size_t n>
-static int index_of(const WideKey (&keys)[n], const WideKey& k) {
-    for (size_t i = 0; i < n; ++i)
-        if (keys[i] == k) return (int)i;
-    return -1;
-}
-
 static IpmParams params(int N, int model, int precision, bool option) {
     IpmParams P{};
     ipopt_default_options(P);
@@ -46,66 +39,115 @@ static IpmParams params(int N, int model, int precision, bool option) {
     return P;
 }
 
-// ------------------------------------------------------------------ the instance table
-static void check_instances() {
-    constexpr size_t ns = sizeof(kSolveKeys) / sizeof(WideKey), nr = sizeof(kResumeKeys) / sizeof(WideKey),
-                     nw = sizeof(kWarmKeys) / sizeof(WideKey);
-    bool used_s[ns] = {}, used_r[nr] = {}, used_w[nw] = {};
-    std::printf("{\n");
+// ------------------------------------------------------------------ the instance list
+static bool g_used[kWideInstances];
+// a chosen key is a row of the list under its kind; the row's index
+static int use(const WideKey& k, int kind, const char* fn, int model, int prec, int N, int opt, long B) {
+    CHECK(k.ok(), "%s refuses model %d precision %d N %d option %d B %ld", fn, model, prec, N, opt, B);
+    const int i = find_key(k);
+    CHECK(k.kind == kind && i >= 0 && kWideKeys[i].kind == kind,
+          "%s of model %d precision %d N %d option %d B %ld is not in the list under its kind", fn, model, prec, N,
+          opt, B);
+    g_used[i] = true;
+    return i;
+}
+static bool same_but_kind(WideKey a, const WideKey& b) {
+    a.kind = b.kind;
+    return a == b;
+}
+
+// Every key function over model x precision x N = 1..128 x default / non-default options x
+// B in {1, 4096, 4097}.  pp_table: prints the per-problem solve instance chosen under a
+// non-default option per (model, horizon range) instead of the solve instances' JSON.
+static void check_instances(bool pp_table) {
+    static_assert(sizeof(kWideNames) / sizeof(kWideNames[0]) == kWideInstances &&
+                  sizeof(kWideGroupOf) / sizeof(kWideGroupOf[0]) == kWideInstances);
+    if (!pp_table) std::printf("{\n");
     bool first = true;
     for (int model = 0; model < 2; ++model)
         for (int prec = 0; prec < 2; ++prec)
             for (int opt = 0; opt < 2; ++opt)
                 for (long B : {1L, 4096L, 4097L}) {
-                    std::printf("%s  \"model%d_precision%d_%s_B%ld\": [", first ? "" : ",\n", model, prec,
-                                opt ? "option" : "default", B);
+                    if (!pp_table)
+                        std::printf("%s  \"model%d_precision%d_%s_B%ld\": [", first ? "" : ",\n", model, prec,
+                                    opt ? "option" : "default", B);
                     first = false;
-                    std::string cur;
-                    int from = 1;
+                    std::string cur, cur_pp;
+                    int from = 1, from_pp = 1;
                     bool f2 = true;
                     for (int N = 1; N <= 129; ++N) {
-                        std::string name = "END";
+                        std::string name = "END", name_pp = "END";
                         if (N <= 128) {
                             const IpmParams P = params(N, model, prec, opt);
                             const WideKey k = solve_key(P, B);
                             const bool refused = prec == 1 && model == 1;  // (fp32: the differential drive)
                             CHECK(k.ok() == !refused, "model %d precision %d N %d", model, prec, N);
+                            CHECK(resume_key(P).ok() == !refused, "resume: model %d precision %d N %d", model, prec, N);
                             name = "";
                             if (k.ok()) {
-                                const int i = index_of(kSolveKeys, k);
-                                CHECK(i >= 0, "solve key of model %d precision %d N %d option %d B %ld not in the list",
-                                      model, prec, N, opt, B);
-                                used_s[i] = true;
-                                name = kSolveNames[i];
-                                const int r = index_of(kResumeKeys, resume_key(P));
-                                CHECK(r >= 0, "resume key of model %d precision %d N %d", model, prec, N);
-                                used_r[r] = true;
-                                if (prec == 1) {
-                                    const int w = index_of(kWarmKeys, warm_key(fp64_params(P)));
-                                    CHECK(w >= 0, "warm key of N %d", N);
-                                    used_w[w] = true;
-                                }
+                                name = kWideNames[use(k, SOLVE, "solve_key", model, prec, N, opt, B)];
+                                use(resume_key(P), RESUME, "resume_key", model, prec, N, opt, B);
+                                if (prec == 1)
+                                    use(warm_key(fp64_params(P)), WARM, "warm_key", model, prec, N, opt, B);
+                            }
+                            // rows and a start: fp32 is refused
+                            const WideKey pk = pp_solve_key(P, B), prk = pp_resume_key(P);
+                            const WideKey sk = start_key(P), srk = start_resume_key(P);
+                            CHECK(pk.ok() == (prec == 0) && prk.ok() == (prec == 0), "rows: model %d precision %d N %d",
+                                  model, prec, N);
+                            CHECK(sk.ok() == (prec == 0) && srk.ok() == (prec == 0), "start: model %d precision %d N %d",
+                                  model, prec, N);
+                            if (prec == 0) {
+                                // fp64, the class and register allocation of the plain general instance
+                                // (the key solve_key gives a non-default option at B = 4097); the
+                                // per-problem default-options instance only under default options
+                                const WideKey plain = solve_key(params(N, model, 0, true), 4097);
+                                CHECK(!plain.f32 && !plain.defopt, "model %d N %d: the plain general instance", model, N);
+                                const int i = use(pk, PP_SOLVE, "pp_solve_key", model, prec, N, opt, B);
+                                CHECK(!pk.f32 && pk.model == plain.model && pk.split == plain.split && pk.nb == plain.nb &&
+                                          pk.wpe == plain.wpe && (!pk.defopt || !opt),
+                                      "model %d N %d: rows, not the plain general instance's class", model, N);
+                                use(prk, PP_RESUME, "pp_resume_key", model, prec, N, opt, B);
+                                CHECK(same_but_kind(prk, resume_key(P)), "per-problem resume key of model %d N %d", model, N);
+                                use(sk, START, "start_key", model, prec, N, opt, B);
+                                CHECK(same_but_kind(sk, plain), "model %d N %d: start, not the plain general instance", model,
+                                      N);
+                                use(srk, START_RESUME, "start_resume_key", model, prec, N, opt, B);
+                                CHECK(same_but_kind(srk, resume_key(P)), "started resume key of model %d N %d", model, N);
+                                name_pp = kWideNames[i];
                             }
                         }
-                        if (N == 1) cur = name;
+                        if (N == 1) cur = name, cur_pp = name_pp;
                         if (name != cur) {
-                            std::printf("%s[%d, %d, \"%s\"]", f2 ? "" : ", ", from, N - 1, cur.c_str());
+                            if (!pp_table) std::printf("%s[%d, %d, \"%s\"]", f2 ? "" : ", ", from, N - 1, cur.c_str());
                             f2 = false;
                             cur = name;
                             from = N;
                         }
+                        if (name_pp != cur_pp) {
+                            if (pp_table && prec == 0 && opt == 1 && B == 4097)
+                                std::printf("model %d N %d..%d %s\n", model, from_pp, N - 1, cur_pp.c_str());
+                            cur_pp = name_pp;
+                            from_pp = N;
+                        }
                     }
-                    std::printf("]");
+                    if (!pp_table) std::printf("]");
                 }
-    std::printf("\n}\n");
+    if (!pp_table) std::printf("\n}\n");
     // no dead instance
-    for (size_t i = 0; i < ns; ++i) CHECK(used_s[i], "solve instance %s is never chosen", kSolveNames[i]);
-    for (size_t i = 0; i < nr; ++i) CHECK(used_r[i], "resume instance %zu is never chosen", i);
-    for (size_t i = 0; i < nw; ++i) CHECK(used_w[i], "warm instance %zu is never chosen", i);
+    for (int i = 0; i < kWideInstances; ++i) CHECK(g_used[i], "instance %s is never chosen", kWideNames[i]);
     // refusals: more than 128 stages
-    CHECK(!solve_key(params(129, 0, 0, false), 1).ok() && !resume_key(params(129, 0, 0, false)).ok() &&
-              !warm_key(params(129, 0, 0, false)).ok(),
+    const IpmParams P129 = params(129, 0, 0, false);
+    CHECK(!solve_key(P129, 1).ok() && !resume_key(P129).ok() && !warm_key(P129).ok() && !pp_solve_key(P129, 1).ok() &&
+              !pp_resume_key(P129).ok() && !start_key(P129).ok() && !start_resume_key(P129).ok(),
           "N = 129");
+    // the groups: 0 .. kWideGroups - 1, none empty
+    bool seen[kWideGroups] = {};
+    for (int g : kWideGroupOf) {
+        CHECK(g >= 0 && g < kWideGroups, "group %d", g);
+        seen[g] = true;
+    }
+    for (int g = 0; g < kWideGroups; ++g) CHECK(seen[g], "group %d has no instance", g);
 }
 
 // ------------------------------------------------------------------ the workspace layout
@@ -244,9 +286,51 @@ static int check_tick_layouts() {
     return cases;
 }
 
-int main() {
-    check_instances();
-    const int cases = check_layouts() + check_tick_layouts();
+// ------------------------------------------------------------------ the host solve's staging
+static int check_io_layouts() {
+    int cases = 0;
+    for (int64_t B : {1, 3, 4096})
+        for (int N : {2, 20, 128})
+            for (int rows : {0, 1})
+                for (int sol : {0, 1})
+                    for (int start : {0, 1}) {
+                        const IoLayout L(B, N, rows, sol, start);
+                        char what[80];
+                        std::snprintf(what, sizeof what, "io B %lld N %d rows %d sol %d start %d", (long long)B, N, rows,
+                                      sol, start);
+                        ++cases;
+                        // the regions in the stated order, each from an 8-byte boundary, none
+                        // overlapping the next; the int32 regions last; the total is the end of the last
+                        const Region* r[] = {&L.state, &L.coeffs, &L.u0,    &L.traj, &L.obj,  &L.mu0, &L.rec,
+                                             &L.rows,  &L.status, &L.iters, &L.diag, &L.mode, &L.used};
+                        CHECK(r[0]->off == 0, "%s", what);
+                        for (int i = 0; i < 13; ++i) {
+                            CHECK(r[i]->off % 8 == 0, "%s: region %d at %zu", what, i, r[i]->off);
+                            if (i > 0) CHECK(r[i]->off == r[i - 1]->end(), "%s: region %d", what, i);
+                        }
+                        CHECK(L.total == L.used.end(), "%s: total", what);
+                        // each holds what it is for
+                        const size_t b = (size_t)B, st = start ? b : 0, ne = (size_t)solution_elems(N);
+                        CHECK(L.state.bytes == 48 * b && L.coeffs.bytes == 32 * b && L.u0.bytes == 16 * b &&
+                                  L.traj.bytes == 24 * (size_t)N * b && L.obj.bytes == 8 * b,
+                              "%s: the solve's", what);
+                        CHECK(L.mu0.bytes == 8 * st && L.rec.bytes == (sol || start ? 8 * ne * b : 0) &&
+                                  L.rows.bytes == (rows ? 8 * 16 * b : 0),
+                              "%s: mu0, records, rows", what);
+                        CHECK(L.status.bytes >= 4 * b && L.status.bytes < 4 * b + 8 && L.iters.bytes >= 4 * b &&
+                                  L.iters.bytes < 4 * b + 8 && L.diag.bytes == 16 * b,
+                              "%s: status, iters, diag", what);
+                        CHECK(L.mode.bytes >= 4 * st && L.mode.bytes < 4 * st + 8 && L.used.bytes >= 4 * st &&
+                                  L.used.bytes < 4 * st + 8,
+                              "%s: mode, used", what);
+                    }
+    return cases;
+}
+
+// (argument "pp": the per-problem table on the standard output instead of the JSON)
+int main(int argc, char** argv) {
+    check_instances(argc > 1 && std::string(argv[1]) == "pp");
+    const int cases = check_layouts() + check_tick_layouts() + check_io_layouts();
     std::fprintf(stderr, "wide_plan_check: %d layouts ok\n", cases);
     return 0;
 }

@@ -1,5 +1,5 @@
 """GPU: a parameter row per problem in one batch (mpcg_solve_pp / mpcg_solve_device_pp, the
-k_solve_wide_pp / k_resume_wide_pp instances) and the tick with Tracking::deceleration
+k_solve_wide_pp / k_resume_wide<PP_RESUME> instances) and the tick with Tracking::deceleration
 (mpcg_track_device_goal), against the oracle called with each row's own parameters.
 
 The handle is always created with other values in every per-problem field
@@ -121,7 +121,7 @@ PARK_ROWS = {"resto_N20": 4, "resto_N40": 12, "bicycle": 6}
 @pytest.mark.parametrize("park_capacity", [0, 1])
 @pytest.mark.parametrize("sname", list(PARK_ROWS))
 def test_rows_across_a_park(torch_cuda, oracle, features_golden, sname, park_capacity):  # noqa: F811
-    """Problems that enter the restoration phase: k_resume_wide_pp rebuilds the row's parameters
+    """Problems that enter the restoration phase: k_resume_wide<PP_RESUME> rebuilds the row's parameters
     for a parked problem and for the re-solve after a park-area overflow (one park entry).  Even
     rows take the recipe, odd rows the set's own parameters -- not the handle's."""
     from mpc_ros_amd import params

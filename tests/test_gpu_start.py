@@ -1,5 +1,5 @@
 """GPU: start point in (mpcg_solve_start / mpcg_solve_device_start; the k_start_wide and
-k_resume_wide_start instances) against the host emulation of the same solver started the same way
+k_resume_wide<START_RESUME> instances) against the host emulation of the same solver started the same way
 (tests/native/wide_start_check.cpp, tests/test_start_host.py).
 
 The problems are the neighbour problems of tests/test_start_host.py's shapes, each started from the
@@ -139,7 +139,7 @@ def test_restoration_rows_do_not_depend_on_the_park_capacity(torch_cuda, oracle,
 def test_started_solves_through_the_parked_and_overflow_paths(torch_cuda, oracle, tmp_path_factory):  # noqa: F811
     """Starts that are not the cold point and restore (test_start_host.restoring_starts, tiled twice:
     four restoring problems among sixteen).  With the default park area all four are continued by
-    k_resume_wide_start from their park entries (diag[:, 2] 1), with one park entry at least three
+    k_resume_wide<START_RESUME> from their park entries (diag[:, 2] 1), with one park entry at least three
     are started again from their records by its overflow branch (2).  Either way the host emulation's
     iterates: a cold restart of the FULL rows would take 80 iterations instead of 70, and a PRIMAL
     row continued with the cold objective scale would report multipliers 1 % off."""
@@ -308,6 +308,43 @@ def test_refusals_leave_the_handle_usable(torch_cuda, oracle, tmp_path_factory):
     for k in ("u0", "status", "iters", "obj", "sol"):
         np.testing.assert_array_equal(h[k], g[k], err_msg=k)
     np.testing.assert_array_equal(h["start_used"], g["used"])
+
+
+def test_host_entries_return_their_device_twins_bytes(torch_cuda, infinity_golden):  # noqa: F811
+    """Each host-pointer entry -- mpcg_solve_ex, _pp, _sol and _start, staged through the handle's io
+    block (wide_plan.h IoLayout) -- returns byte for byte what its device-pointer twin returns, for
+    every output, with rows, records, mu0, diag and start_used all given.  B is odd, so the int32
+    regions of the block end off an 8-byte boundary."""
+    from conftest import params_from_array
+    from mpc_ros_amd import params
+
+    torch = torch_cuda
+    gi = infinity_golden
+    P = params_from_array(gi["params"])
+    B = 3
+    st, cf = np.ascontiguousarray(gi["state"][:B]), np.ascontiguousarray(gi["coeffs"][:B])
+    rows = params.rows([P, dict(P, REF_V=0.7 * P["REF_V"], W_CTE=2.0 * P["W_CTE"], ANGVEL=0.5 * P["ANGVEL"]), P])
+    s = solver_for(P)
+    assert s.N == 20
+    outs = ("u0", "traj", "status", "obj", "iters", "diag")
+
+    def same(h, g, keys):
+        for k in keys:
+            assert h[k].dtype == g[k].dtype and h[k].tobytes() == g[k].tobytes(), k
+
+    same(s.solve(st, cf), gpu_solve(torch, s, st, cf, want_sol=False), outs)
+    assert s.last_kernel.startswith("k_solve_wide<")
+    same(s.solve(st, cf, params_rows=rows), gpu_solve(torch, s, st, cf, rows=rows, want_sol=False), outs)
+    assert s.last_kernel.startswith("k_solve_wide_pp<")
+    g = gpu_solve(torch, s, st, cf, rows=rows)
+    same(s.solve(st, cf, params_rows=rows, want_solution=True), g, outs + ("sol",))
+    modes = mixed_modes(B)
+    gs = gpu_start(torch, s, st, cf, g["sol"], modes, mu0=MU0, rows=rows)
+    hs = s.solve(st, cf, params_rows=rows, want_solution=True, start=g["sol"], start_mode=modes, mu0=MU0)
+    assert s.last_kernel.startswith("k_start_wide<")
+    same(hs, gs, outs + ("sol",))
+    same({"used": hs["start_used"]}, gs, ("used",))
+    assert not np.array_equal(gs["iters"], g["iters"])  # (the start was read)
 
 
 # ------------------------------------------------------------------ 9. class MPC

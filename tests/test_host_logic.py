@@ -95,26 +95,31 @@ def test_build_reads_kernel_resource_remarks():
 
 def test_parallel_build_units_cover_every_instance_group():
     """The parallel build compiles mpcg_wide_inst.hip once per group: the groups it names are
-    exactly the groups of the instance lists in wide_plan.h (a group without a unit would
+    exactly the groups of the instance list in wide_plan.h (a group without a unit would
     leave its kernels undefined at link time; a unit without instances is wasted), and every
-    solve instance's (model, split, blocks) has an fp64 resume instance (its parked problems, and
-    the fp32 solver's escalations)."""
+    batch instance's (model, split, blocks) has an fp64 resume instance of its own kind (its
+    parked problems, and the fp32 solver's escalations): the solve and warm instances among the
+    RESUME rows, the per-problem ones among PP_RESUME, the started ones among START_RESUME."""
     import re
 
     from mpc_ros_amd import build
 
     text = open(os.path.join(build.CSRC, "wide_plan.h")).read()
-    solve = re.findall(r"X\((\d+), (\d), (true|false), (double|float), (\d), (true|false), (\d)\)", text)
-    resume = re.findall(r"X\((\d+), (\d), (true|false), (double|float), (\d)\)", text)
-    assert solve and resume
-    groups = {int(g[0]) for g in solve} | {int(g[0]) for g in resume}
+    rows = re.findall(r"X\((\d+), ([A-Z_]+), (\d), (true|false), (double|float), (\d), (true|false), (\d)\)", text)
+    resume_of = {"SOLVE": "RESUME", "WARM": "RESUME", "PP_SOLVE": "PP_RESUME", "START": "START_RESUME"}
+    kinds = {r[1] for r in rows}
+    assert kinds == set(resume_of) | set(resume_of.values())
+    groups = {int(r[0]) for r in rows}
     units = [u for u in build.compile_units() if u[0] == build.INST]
     assert sorted(int(u[1][0].split("=")[1]) for u in units) == sorted(groups) == list(range(build.N_INST))
-    res = {tuple(r[1:]) for r in resume}
-    for _g, m, sp, ty, nb, _d, _w in solve:
-        # (the fp32 solver's problems that need the restoration phase are solved again by the
-        # fp64 resume instance of the same horizon)
-        assert (m, sp, "double", nb) in res
+    for kind, rkind in resume_of.items():
+        batch = [r for r in rows if r[1] == kind]
+        res = {tuple(r[2:6]) for r in rows if r[1] == rkind}
+        assert batch and res
+        for _g, _k, m, sp, ty, nb, _d, _w in batch:
+            # (the fp32 solver's problems that need the restoration phase are solved again by the
+            # fp64 resume instance of the same horizon)
+            assert (m, sp, "double", nb) in res, (kind, m, sp, nb)
     # every source of the library is compiled exactly once besides the instance groups
     others = [u[0] for u in build.compile_units() if u[0] != build.INST]
     assert sorted(others) == sorted(s for s in build.SOURCES if s != build.INST)
@@ -122,10 +127,12 @@ def test_parallel_build_units_cover_every_instance_group():
 
 def test_launch_plan_native_check(tmp_path):
     """tests/native/wide_plan_check.cpp (mpc_ros_amd/csrc/wide_plan.h on the host, no GPU
-    runtime): every chosen solve / resume / warm key is an instance the library carries and
-    every instance is chosen by some input; the workspace layout's regions are in order, aligned
+    runtime): every key chosen by any of the seven key functions is a row of the instance list
+    under its kind and every row is chosen by some input; the started kind's key is the plain
+    general-options key; the workspace layout's regions are in order, aligned
     and disjoint for every horizon class, precision, park capacity and batch size, and so are the
-    regions of a control tick's scratch (TickLayout) over B x Mmax x rows or none.  The solve
+    regions of a control tick's scratch (TickLayout) over B x Mmax x rows or none and of the host
+    solve's staging (IoLayout) over B x N x rows, sol, start or none.  The solve
     instance it chooses over model x precision x N = 1..128 x default / non-default options x
     B in {1, 4096, 4097} equals the recorded choice of the dispatcher before the plan was a
     header (tests/golden/launch_plan.json), which holds the names the GPU tests pin."""

@@ -1,6 +1,6 @@
 """Per-problem parameter rows, host side (no GPU): the row layout of include/mpcg.h
 (MPCG_PP_*), mpcg_pparams_fill / mpcg_pparams_check, params.rows, Tracking::deceleration's rule
-(mpcg_decelerate) and the per-problem launch plan (tests/native/pp_plan_check.cpp).
+(mpcg_decelerate) and the per-problem launch plan (tests/native/wide_plan_check.cpp).
 
 Also the parameter recipe the GPU tests (tests/test_gpu_pparams.py) share: rows that differ from
 each other and from the handle in every per-problem field.
@@ -215,12 +215,13 @@ def test_decelerate_rule(libmpcg):
 
 
 def test_pp_plan_native_check(tmp_path):
-    """tests/native/pp_plan_check.cpp: every pp_solve_key / pp_resume_key over model x N = 1..128
-    x default / non-default options x B in {1, 4096, 4097} is an instance of the per-problem lists,
-    every instance of those lists is chosen by some input, and fp32 is refused."""
-    exe = str(tmp_path / "pp_plan_check")
+    """tests/native/wide_plan_check.cpp (which checks every kind of instance): every pp_solve_key /
+    pp_resume_key over model x N = 1..128 x default / non-default options x B in {1, 4096, 4097} is
+    a row of the instance list under its kind, every row is chosen by some input, and fp32 is
+    refused; with "pp" it prints the per-problem instance chosen under a non-default option."""
+    exe = str(tmp_path / "wide_plan_check")
     subprocess.check_call(["g++", "-O1", "-std=c++20", "-w", "-I", os.path.join(ROOT, "include"), "-o", exe,
-                           os.path.join(ROOT, "tests", "native", "pp_plan_check.cpp")])
-    r = subprocess.run([exe], capture_output=True, text=True)
+                           os.path.join(ROOT, "tests", "native", "wide_plan_check.cpp")])
+    r = subprocess.run([exe, "pp"], capture_output=True, text=True)
     assert r.returncode == 0, r.stderr
     assert "k_solve_wide_pp<0,true,double,1,false,2>" in r.stdout

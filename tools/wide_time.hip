@@ -78,8 +78,8 @@ int main(int argc, char** argv) {
         ws.aux = getenv("WT_SEQ") ? nullptr : aux;
         ws.ev_fork = evf;
         ws.ev_join = evj;
-        CK(mpcg::launch_wide_solve(P, B, dst, dcf, du0, nullptr, dss, dobj, dit, nullptr, order, dspill,
-                                   mpcg::wide_spill_bytes(P, B), 0, ws));
+        const mpcg::SolveRequest rq{B, dst, dcf, nullptr, du0, nullptr, dss, dobj, dit};
+        CK(mpcg::launch_wide_solve(P, rq, order, dspill, mpcg::wide_spill_bytes(P, B), 0, ws));
         CK(hipEventRecord(e1));
         CK(hipEventSynchronize(e1));
         float ms = 0;
