@@ -14,7 +14,8 @@ import subprocess
 import numpy as np
 import pytest
 
-from conftest import ROOT, params_from_array
+from conftest import params_from_array
+from host_harness import build, harness_stdin, opts_line
 
 # The emulation runs the 64 lanes of a problem as fibers on one thread (a round-robin hand-off
 # per lane exchange) and the problems of a call in parallel, one thread each: every fixture
@@ -27,36 +28,6 @@ def subset(g, rows):
     keys = ("state", "coeffs", "u0", "traj", "obj", "status", "iters", "diag")
     rows = np.arange(len(g["status"])) if FULL else np.asarray(rows)
     return {k: g[k][rows] for k in keys if k in g}
-
-
-# fields of the oracle's IpmOpts that are no option of the device core
-ORACLE_ONLY = ("honor_original_bounds", "print_level", "kkt_structured", "refine_steps")
-
-
-def opts_line(o, filter_cap=64) -> str:
-    """The harness's Ipopt-option lines from an oracle IpmOpts: every field under its own name
-    (same values both sides; restoration = 0 is the core's no_restoration = 1), closed by "end".
-    The harness refuses a name the core does not have."""
-    lines = [f"filter_cap {int(filter_cap)}"]
-    for name, _ in o._fields_:
-        if name in ORACLE_ONLY:
-            continue
-        if name == "restoration":
-            lines.append(f"no_restoration {0 if o.restoration else 1}")
-        else:
-            lines.append(f"{name} {getattr(o, name)!r}")
-    return "\n".join(lines + ["end"])
-
-
-def harness_stdin(P, state, coeffs, o, options) -> str:
-    """The harness's input: the two problem lines, the option lines, the problems."""
-    hdr = (f"{int(P['STEPS'])} {P['DT']!r} {P['REF_CTE']!r} {P['REF_ETHETA']!r} {P['REF_V']!r} {P['W_CTE']!r} "
-           f"{P['W_EPSI']!r} {P['W_V']!r} {P['W_ANGVEL']!r} {P['W_A']!r} {P['W_DANGVEL']!r} {P['W_DA']!r} "
-           f"{P['ANGVEL']!r} {P['MAXTHR']!r} {P['BOUND']!r} {o.tol!r} {o.max_iter}\n"
-           f"{int(P.get('MODEL', 0))} {float(P.get('LF', 0.5))!r}\n{options}\n{len(state)}\n")
-    body = "\n".join(" ".join(repr(float(v)) for v in np.concatenate([state[b], coeffs[b]]))
-                     for b in range(len(state)))
-    return hdr + body + "\n"
 
 
 def run_harness(exe, P, state, coeffs, opts=None, env=None, filter_cap=64):
@@ -99,17 +70,9 @@ def compare(r, g, atol=1e-9, iters_exact=1.0):
 # wavefront: stage-parallel sweeps, 64-lane Riccati) with 64 fibers standing in for the
 # lanes.  Summation orders differ from the oracle's (tree reductions), so the
 # comparison is to rounding: same status and iteration count, controls within 1e-9.
-_harness_exe = []  # (built once per session: tests/test_option_matrix.py uses the same fixture)
-
-
 @pytest.fixture(scope="module")
-def wide_harness(tmp_path_factory):
-    if not _harness_exe:
-        exe = str(tmp_path_factory.mktemp("whc") / "wide_host_check")
-        subprocess.check_call(["g++", "-O2", "-std=c++20", "-w", "-pthread", "-o", exe,
-                               os.path.join(ROOT, "tests", "native", "wide_host_check.cpp")])
-        _harness_exe.append(exe)
-    return _harness_exe[0]
+def wide_harness():
+    return build("wide_host_check")  # (built once per session: tests/test_option_matrix.py uses the same fixture)
 
 
 def test_wide_core_matches_oracle_infinity_subset(wide_harness, infinity_golden):

@@ -12,16 +12,15 @@ outputs, wide_core.h FUSE_SQ).
 """
 from __future__ import annotations
 
-import os
 import subprocess
 
 import numpy as np
 import pytest
 
-from conftest import ROOT, params_from_array
-from test_core_host import fp32_opts, harness_stdin, opts_line
+from conftest import params_from_array
+from host_harness import build_all, harness_stdin, opts_line
+from test_core_host import fp32_opts
 
-SRC = os.path.join(ROOT, "tests", "native", "wide_fused_check.cpp")
 # rows of the infinity fixture set the GPU test (tests/test_gpu_fused_sweeps.py) runs for their
 # rare paths: INERTIA_ROW repeats Newton solves with a Hessian perturbation (and takes no
 # second-order correction), SOC_ROW accepts second-order corrections
@@ -29,19 +28,11 @@ INERTIA_ROW, SOC_ROW = 9, 7
 
 
 @pytest.fixture(scope="module")
-def programs(tmp_path_factory):
+def programs():
     """{(dtype, fused)}: the four builds of the harness."""
-    d = tmp_path_factory.mktemp("wfc")
-    procs, exes = [], {}
-    for ty in ("double", "float"):
-        for fused in (True, False):
-            exe = str(d / f"wfc_{ty}_{'fused' if fused else 'separate'}")
-            cmd = ["g++", "-O2", "-std=c++20", "-w", "-pthread", f"-DHOST_T={ty}", "-o", exe, SRC]
-            procs.append(subprocess.Popen(cmd + ([] if fused else ["-DMPCG_FUSE=0"])))
-            exes[ty, fused] = exe
-    for p in procs:
-        assert p.wait() == 0
-    return exes
+    keys = [(ty, fused) for ty in ("double", "float") for fused in (True, False)]
+    flags = [(f"-DHOST_T={ty}",) + (() if fused else ("-DMPCG_FUSE=0",)) for ty, fused in keys]
+    return dict(zip(keys, build_all("wide_fused_check", flags)))
 
 
 def run(exe, P, state, coeffs, o):

@@ -11,13 +11,10 @@ parameters change between solves.
 """
 from __future__ import annotations
 
-import os
-import subprocess
-
 import numpy as np
 import pytest
 
-from conftest import ROOT
+from host_harness import build
 from test_core_host import FILTER_PEAKS, fp32_opts, run_harness
 from test_gpu_parity import check_against, solver_for, torch_cuda  # noqa: F401
 from test_option_matrix import CASES, TABLE, case_params, case_problems, oracle_case, oracle_opts
@@ -175,11 +172,8 @@ def test_filter_cap_does_not_change_results(torch_cuda, features_golden, cap):  
 
 # ------------------------------------------------------------------ e. the fp32 solver alone
 @pytest.fixture(scope="module")
-def float_harness(tmp_path_factory):
-    exe = str(tmp_path_factory.mktemp("whc32") / "wide_host_check_f32")
-    subprocess.check_call(["g++", "-O2", "-std=c++20", "-w", "-pthread", "-DHOST_T=float", "-o", exe,
-                           os.path.join(ROOT, "tests", "native", "wide_host_check.cpp")])
-    return exe
+def float_harness():
+    return build("wide_host_check", "-DHOST_T=float")
 
 
 @pytest.mark.parametrize("name", ["N40", "infinity"])

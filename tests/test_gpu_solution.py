@@ -18,8 +18,9 @@ import numpy as np
 import pytest
 
 from conftest import params_from_array
+from host_harness import build
 from test_gpu_parity import solver_for, torch_cuda  # noqa: F401
-from test_solution_host import fixture_set, run_sol_harness, sol_harness, split
+from test_solution_host import fixture_set, run_sol_harness, split
 
 pytestmark = pytest.mark.gpu
 
@@ -91,7 +92,7 @@ def shape_cases(infinity_golden):
 @pytest.fixture(scope="module")
 def host_records(oracle, infinity_golden, tmp_path_factory):
     """The host emulation's records of every shape, computed once and left unchanged."""
-    exe = sol_harness(tmp_path_factory)
+    exe = build("wide_sol_check")
     out = {}
     for name, (P, st, cf) in shape_cases(infinity_golden).items():
         st, cf = np.ascontiguousarray(st), np.ascontiguousarray(cf)
@@ -135,7 +136,7 @@ def test_rows_and_an_invalid_row(torch_cuda, host_records, oracle, tmp_path_fact
     rows[2] = 0.0
     r = gpu_solve(torch_cuda, solver_for(dict(P, REF_V=0.1, W_V=7.0)), st, cf, rows=rows)
     assert r["status"][2] == 13 and (r["sol"][2] == 0).all() and (r["u0"][2] == 0).all()
-    exe = sol_harness(tmp_path_factory)
+    exe = build("wide_sol_check")
     for b, Pb in ((0, P), (1, P2)):
         hb = run_sol_harness(exe, Pb, st[b:b + 1], cf[b:b + 1], oracle.ref_opts(20))
         rb = {k: v[b:b + 1] for k, v in r.items()}

@@ -125,7 +125,7 @@ def test_parallel_build_units_cover_every_instance_group():
     assert sorted(others) == sorted(s for s in build.SOURCES if s != build.INST)
 
 
-def test_launch_plan_native_check(tmp_path):
+def test_launch_plan_native_check():
     """tests/native/wide_plan_check.cpp (mpc_ros_amd/csrc/wide_plan.h on the host, no GPU
     runtime): every key chosen by any of the seven key functions is a row of the instance list
     under its kind and every row is chosen by some input; the started kind's key is the plain
@@ -140,11 +140,10 @@ def test_launch_plan_native_check(tmp_path):
     import re
     import subprocess
 
+    import host_harness
     from conftest import ROOT as root
 
-    exe = str(tmp_path / "wide_plan_check")
-    subprocess.check_call(["g++", "-O1", "-std=c++20", "-w", "-o", exe,
-                           os.path.join(root, "tests", "native", "wide_plan_check.cpp")])
+    exe = host_harness.build("wide_plan_check", "-O1")
     r = subprocess.run([exe], capture_output=True, text=True)
     assert r.returncode == 0, r.stderr
     with open(os.path.join(root, "tests", "golden", "launch_plan.json")) as f:

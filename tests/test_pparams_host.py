@@ -16,6 +16,7 @@ import numpy as np
 import pytest
 
 from conftest import ROOT
+from host_harness import build
 
 PHI = 0.6180339887498949
 WEIGHTS = ("W_CTE", "W_EPSI", "W_V", "W_ANGVEL", "W_A", "W_DANGVEL", "W_DA")
@@ -214,14 +215,12 @@ def test_decelerate_rule(libmpcg):
     assert f(0.01, 0.8, thr, vmax, vmin, 1.0) == vmin
 
 
-def test_pp_plan_native_check(tmp_path):
+def test_pp_plan_native_check():
     """tests/native/wide_plan_check.cpp (which checks every kind of instance): every pp_solve_key /
     pp_resume_key over model x N = 1..128 x default / non-default options x B in {1, 4096, 4097} is
     a row of the instance list under its kind, every row is chosen by some input, and fp32 is
     refused; with "pp" it prints the per-problem instance chosen under a non-default option."""
-    exe = str(tmp_path / "wide_plan_check")
-    subprocess.check_call(["g++", "-O1", "-std=c++20", "-w", "-I", os.path.join(ROOT, "include"), "-o", exe,
-                           os.path.join(ROOT, "tests", "native", "wide_plan_check.cpp")])
+    exe = build("wide_plan_check", "-O1")
     r = subprocess.run([exe, "pp"], capture_output=True, text=True)
     assert r.returncode == 0, r.stderr
     assert "k_solve_wide_pp<0,true,double,1,false,2>" in r.stdout

@@ -28,14 +28,13 @@ def test_oracle_under_asan_ubsan(tmp_path):
     assert r.stdout.count("status 1 ") >= 5
 
 
-def test_wide_core_host_emulation_under_asan_ubsan(tmp_path, variants_golden):
+def test_wide_core_host_emulation_under_asan_ubsan(variants_golden):
+    from host_harness import build
     from test_core_host import compare, run_harness
 
     from conftest import params_from_array
 
-    exe = str(tmp_path / "whc_san")
-    subprocess.check_call(["g++", "-std=c++20", "-w", "-pthread", *SAN, "-o", exe,
-                           os.path.join(ROOT, "tests", "native", "wide_host_check.cpp")])
+    exe = build("wide_host_check", *SAN)
     g = variants_golden["N3"]
     sub = {k: g[k][:2] for k in ("state", "coeffs", "u0", "traj", "obj", "status", "iters", "diag")}
     old = dict(os.environ)

@@ -13,33 +13,24 @@ FUSE_RC follows FUSE_SQ).
 """
 from __future__ import annotations
 
-import os
 import subprocess
 
 import numpy as np
 import pytest
 
-from conftest import ROOT, params_from_array
-from test_core_host import fp32_opts, harness_stdin, opts_line
+from conftest import params_from_array
+from host_harness import build_all, harness_stdin, opts_line
+from test_core_host import fp32_opts
 from test_fused_sweeps_host import SETS, fixture_sets
 
-SRC = os.path.join(ROOT, "tests", "native", "wide_slack_check.cpp")
 
 
 @pytest.fixture(scope="module")
-def programs(tmp_path_factory):
+def programs():
     """{(dtype, kept)}: the four builds of the harness."""
-    d = tmp_path_factory.mktemp("wsc")
-    procs, exes = [], {}
-    for ty in ("double", "float"):
-        for kept in (True, False):
-            exe = str(d / f"wsc_{ty}_{'kept' if kept else 'formed'}")
-            cmd = ["g++", "-O2", "-std=c++20", "-w", "-pthread", f"-DHOST_T={ty}", "-o", exe, SRC]
-            procs.append(subprocess.Popen(cmd + ([] if kept else ["-DMPCG_FUSE=3"])))
-            exes[ty, kept] = exe
-    for p in procs:
-        assert p.wait() == 0
-    return exes
+    keys = [(ty, kept) for ty in ("double", "float") for kept in (True, False)]
+    flags = [(f"-DHOST_T={ty}",) + (() if kept else ("-DMPCG_FUSE=3",)) for ty, kept in keys]
+    return dict(zip(keys, build_all("wide_slack_check", flags)))
 
 
 def run(exe, P, state, coeffs, o):

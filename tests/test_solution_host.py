@@ -19,16 +19,14 @@ not compile without solution_out.
 """
 from __future__ import annotations
 
-import os
 import subprocess
 
 import numpy as np
 import pytest
 
-from conftest import ROOT, load_npz, params_from_array
-from test_core_host import harness_stdin, opts_line
+from conftest import load_npz, params_from_array
+from host_harness import build, harness_stdin, opts_line
 
-SRC = os.path.join(ROOT, "tests", "native", "wide_sol_check.cpp")
 X_ATOL = 1e-7
 # the largest dual residual / oracle kkt_inf over the status-1 rows of SETS, measured on the host
 # emulation (test_multipliers_satisfy_kkt prints the figure of every set: 2.9e2 on the infinity rows,
@@ -58,17 +56,6 @@ def fixture_set(name):
     z = load_npz(fname)
     g = {k.split("__", 1)[1]: v for k, v in z.items() if k.startswith(key + "__")}
     return params_from_array(g["params"]), g
-
-
-_exe = []
-
-
-def sol_harness(tmp_path_factory):
-    if not _exe:
-        exe = str(tmp_path_factory.mktemp("wsc") / "wide_sol_check")
-        subprocess.check_call(["g++", "-O2", "-std=c++20", "-w", "-pthread", "-o", exe, SRC])
-        _exe.append(exe)
-    return _exe[0]
 
 
 def run_sol_harness(exe, P, state, coeffs, o):
@@ -132,7 +119,7 @@ def records(name, oracle, tmp_path_factory):
         N = int(P["STEPS"])
         o = oracle.ref_opts(N)
         state, coeffs = np.ascontiguousarray(g["state"]), np.ascontiguousarray(g["coeffs"])
-        r = run_sol_harness(sol_harness(tmp_path_factory), P, state, coeffs, o)
+        r = run_sol_harness(build("wide_sol_check"), P, state, coeffs, o)
         ref = [oracle.mpc_solve(P, state[b], coeffs[b], opts=o, full=True) for b in range(len(state))]
         nk = [numpy_kkt(oracle, P, state[b], coeffs[b], r["sol"][b]) for b in range(len(state))]
         r.update(P=P, N=N, opts=o, state=state, coeffs=coeffs, ref_x=np.array([q["x"] for q in ref]),

@@ -23,10 +23,9 @@ import numpy as np
 import pytest
 
 from conftest import ROOT
-from test_core_host import harness_stdin, opts_line
+from host_harness import build, harness_stdin, opts_line
 from test_solution_host import fixture_set, split
 
-SRC = os.path.join(ROOT, "tests", "native", "wide_start_check.cpp")
 SHIM = os.path.join(ROOT, "tests", "native", "start_oracle.c")
 COLD, PRIMAL, FULL = 0, 1, 2
 X_ATOL = 1e-7   # the cold parity tests' bound on x
@@ -74,17 +73,6 @@ def cold_point(state, N):
     return rec
 
 
-_exe = []
-
-
-def start_harness(tmp_path_factory):
-    if not _exe:
-        exe = str(tmp_path_factory.mktemp("wstc") / "wide_start_check")
-        subprocess.check_call(["g++", "-O2", "-std=c++20", "-w", "-pthread", "-o", exe, SRC])
-        _exe.append(exe)
-    return _exe[0]
-
-
 def run_start(exe, P, state, coeffs, o, modes, starts, mu0=MU0, cold_scaling=0):
     N, B = int(P["STEPS"]), len(state)
     modes = np.broadcast_to(np.asarray(modes, dtype=np.int64), (B,))
@@ -118,7 +106,7 @@ def case(name, oracle, tmp_path_factory):
         P, state, coeffs = shape(name)
         N = int(P["STEPS"])
         o = oracle.ref_opts(N)
-        exe = start_harness(tmp_path_factory)
+        exe = build("wide_start_check")
         zero = np.zeros((len(state), 3 * (8 * N - 2) + 6 * N))
         cold = run_start(exe, P, state, coeffs, o, COLD, zero)
         ns, nc = neighbour(state, coeffs)
@@ -191,11 +179,11 @@ def test_primal_from_cold_point_is_the_cold_solve(cs):
 
 def test_cold_mode_is_the_solution_harness(oracle, tmp_path_factory):
     """The COLD rows against tests/native/wide_sol_check.cpp, which knows no start."""
-    from test_solution_host import run_sol_harness, sol_harness
+    from test_solution_host import run_sol_harness
 
     for name in ("variants_N3", "resto_N20"):
         r = case(name, oracle, tmp_path_factory)
-        ref = run_sol_harness(sol_harness(tmp_path_factory), r["P"], r["state"], r["coeffs"], r["opts"])
+        ref = run_sol_harness(build("wide_sol_check"), r["P"], r["state"], r["coeffs"], r["opts"])
         for k in ("status", "iters", "obj", "u0", "sol"):
             np.testing.assert_array_equal(r["cold"][k], ref[k], err_msg=k)
         assert (r["cold"]["used"] == COLD).all()
