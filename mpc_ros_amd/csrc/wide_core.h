@@ -38,6 +38,12 @@
 #ifndef MPCG_FUSE
 #define MPCG_FUSE 15
 #endif
+// The Riccati sweep with the affine part as a ninth column of its lane grid (WideSolver::RIC9;
+// 0 keeps the sweep in which every lane of a row forms p_i --
+// tests/native/wide_ric_check.cpp compares the settings).
+#ifndef MPCG_RIC9
+#define MPCG_RIC9 1
+#endif
 
 namespace mpcg {
 
@@ -315,6 +321,11 @@ struct WideSolver : RcRegs<TT, wide_fuse_rc<SPLIT, TT, RCK>()> {
     static constexpr bool FUSE_SQ = SPLIT && sizeof(TT) == 8 && (MPCG_FUSE & 1) != 0;
     static constexpr bool FUSE_RED = SPLIT && sizeof(TT) == 8 && (MPCG_FUSE & 2) != 0;
     int sq_ok = 0;
+    // RIC9: riccati9() is the sweep (the restoration problem keeps riccati()'s body: its soft rows
+    // read p from the lanes of the 8 x 8 map).  fp64 only, as FUSE_SQ: on the device the fp32
+    // instance compiles the new sweep to other contractions, and its outputs move with them
+    // (fp32, N = 40: 681 of 65,536 iteration counts).
+    static constexpr bool RIC9 = !RESTO && sizeof(TT) == 8 && (MPCG_RIC9) != 0;
     MPCG_HD void sq_drop() {
         if constexpr (FUSE_SQ) sq_ok = 0;
     }
@@ -1557,7 +1568,9 @@ struct WideSolver : RcRegs<TT, wide_fuse_rc<SPLIT, TT, RCK>()> {
     // Riccati sweep.  Lane (i, j) owns entry (i, j) of the cost-to-go matrix P (and
     // keeps p_i); P lives only in a 64-entry scratch for the row reads of the next
     // stage: the forward pass needs only the gains, and the multipliers come from the
-    // adjoint recursion (forward()).
+    // adjoint recursion (forward()).  (RIC9: the stage-data pass here, the sweep in riccati9();
+    // the body below is the restoration problem's and the fp32 solver's, and every solver's
+    // with -DMPCG_RIC9=0.)
     MPCG_HD bool riccati(int mode, T delta_w) {
         const int t = wv.lane();  // (recomputed per phase: nothing lane-dependent is hoisted)
         wv.sync();
@@ -1569,6 +1582,7 @@ struct WideSolver : RcRegs<TT, wide_fuse_rc<SPLIT, TT, RCK>()> {
             if constexpr (FUSE_SQ) sq_ok = wv.uni(mode == 0 && delta_w == (T)0);
         }
         if constexpr (SPLIT) wv.mark(sq_have ? 14 : 15);  // (the stage-data pass skipped / run)
+        if constexpr (RIC9) return riccati9(mode);
         typedef WideLayout W_;
         const int i = t >> 3, j = t & 7;
         const int si = aslot(i), sj = aslot(j);
@@ -1716,6 +1730,182 @@ struct WideSolver : RcRegs<TT, wide_fuse_rc<SPLIT, TT, RCK>()> {
         if constexpr (RESTO) {
             soft_rows(0, Pij, pvi, bad);  // the initial-state rows (soft as well)
             wv.gsync();                   // (the gains M, m in HBM are read by other lanes in forward())
+        }
+        // a failed inertia test anywhere (the stages after it computed values the retry overwrites)
+        if (wv.uni(bad)) {
+            wv.mark(2);
+            return false;
+        }
+        wv.mark(2);
+        return true;
+    }
+
+    // The sweep with the affine part p as a ninth column of the lane grid (RIC9; riccati() has
+    // run the stage-data pass).  The product M = P' G keeps the 8 x 8 map above -- all 64
+    // entries of M are needed, and the G staging is written with it.  From the M-column reads
+    // to the store of the cost-to-go, lane t < 63 owns entry (i2, j2) = (t / 9, t % 9) of
+    // [P | p], rows 0..6: a column-8 lane runs the instruction stream of a P column on p's
+    // operands -- M's column 7 (h) for the column j, the stage's (r_0, r_1) for the
+    // rate-coupling addends, q_i for the diagonal -- which are, term for term, the p expressions
+    // of riccati() above (an addend that expression does not have is -0.0: x + -0.0 = x for
+    // every x).  Row 7 (the previous acceleration) has no dynamics: its A_hat column and its
+    // Q_hat entries are zero, so q_hat + (A_hat^T M) is bitwise row 6's, and the row-6 lane
+    // forms row 7's entry from its own with (s0i, s1i) = (0, C1).  Lane 63 repeats lane 62.
+    // p, the coupling pairs and the -0.0 live in the M scratch's padding (two doubles per
+    // column, 16-byte aligned): p_i at column i / 2, (C0, 0) at column 4, (0, C1) at column 5,
+    // -0.0 at column 6.
+    MPCG_HD bool riccati9(int mode) {
+        const int t = wv.lane();  // (recomputed per phase: nothing lane-dependent is hoisted)
+        typedef WideLayout W_;
+        constexpr int MS = WideLayout::MS;
+        const int sm = L.SCR(), sp = L.PSC();
+        // the 8 x 8 map: M's entry (i, j), the G staging
+        const int i = t >> 3, j = t & 7;
+        const int gj = sm + MS * j;
+        const int gsrc = goff(i, j);
+        const int gst = sm + MS * i + j;
+        const int pa = j == 7 ? sm + MS * (i >> 1) + 8 + (i & 1) : L.ZB();  // p'_i into M's column 7
+        const int ac0 = sm + MS * 4 + 8, ac1 = sm + MS * 5 + 8, anz = sm + MS * 6 + 8;
+        // the 7 x 9 map
+        const int t2 = t < 63 ? t : 62;
+        const int i2 = t2 / 9, j2 = t2 - 9 * i2;
+        const bool c8 = j2 == 8;
+        const int si = aslot(i2), sj = c8 ? 7 : aslot(j2);
+        const int mi = si >= 0 ? sm + MS * si : L.ZB(), mj = sj >= 0 ? sm + MS * sj : L.ZB();
+        // the rate-coupling entries of S_tilde (see riccati()); row 7's (s0i, s1i) as row 7's
+        // lanes formed them: tw (0 + 0) + 0 + 0 and dt 0 + 0 + C1
+        const T C0 = mode == 0 ? -sf * (T)(2.0 * P.w_dw) : (T)0;
+        const T C1 = mode == 0 ? -sf * (T)(2.0 * P.w_da) : (T)0;
+        const T cc0i = i2 == 6 ? C0 : (T)0, cc1i = 0;
+        const T s07 = 0, s17 = (T)0 + C1;
+        // the column's addend pair (cc0j, cc1j): one 16-byte load at cca + ccs k
+        const int cca = c8 ? L.ST(0) + W_::SQV + 6 : (j2 == 6 ? ac0 : (j2 == 7 ? ac1 : L.ZB()));
+        const int ccs = c8 ? L.SS : 0;
+        // the store of [P | p]'s entry, and row 7's by the row-6 lanes (the other lanes' lands in
+        // their own slot, which the store after it overwrites)
+        const int ao = c8 ? sm + MS * (i2 >> 1) + 8 + (i2 & 1) : sp + 8 * i2 + j2;
+        const int a7 = i2 == 6 ? (c8 ? sm + MS * 3 + 9 : sp + 56 + j2) : ao;
+        // the gains' store at ga0 + gak * k: rows 0, 1 of the map are K[0][j2] | kff[0] and
+        // K[1][j2] | kff[1]; the other lanes store into their own slot of the G staging, which
+        // they overwrite right after
+        const bool gl = i2 < 2;
+        const int go = c8 ? W_::KF + i2 : 8 * i2 + j2;
+        const int ga0 = gl ? L.KR(0) + go : gst;
+        const int gak = gl ? WideLayout::KS : 0;
+        T* const gk = spill + L.SP_KRG() + (gl ? go : 0);  // (KL = 0: the gain records in the workspace)
+        const bool khbm = kr_hbm();
+        // (v, w) curvature of the Lagrangian: S_tilde(0, 3) (bicycle; zero otherwise, -0.0 for p)
+        const int hja = c8 ? anz : L.ST(0) + (j2 == 3 ? W_::SHVD : W_::SZERO), hjs = c8 ? 0 : L.SS;
+        const int hvi = i2 == 3 ? W_::SHVD : W_::SZERO;
+        // Q_hat(i2, j2): diagonal, constraint curvature; column 8: q_i and -0.0
+        const int q1 = c8 ? (i2 < 6 ? W_::SQV + i2 : W_::SZERO) : ((i2 == j2 && i2 < 6) ? W_::SQD + i2 : W_::SZERO);
+        int q2 = W_::SZERO;
+        q2 = (i2 == 0 && j2 == 0) ? W_::SCV + 0 : q2;
+        q2 = (i2 == 2 && j2 == 2) ? W_::SCV + 1 : q2;
+        q2 = ((i2 == 3 && j2 == 2) || (i2 == 2 && j2 == 3)) ? W_::SCV + 2 : q2;
+        q2 = (i2 == 5 && j2 == 5) ? W_::SCV + 3 : q2;
+        q2 = ((i2 == 5 && j2 == 3) || (i2 == 3 && j2 == 5)) ? W_::SCV + 4 : q2;
+        const int q2a = c8 ? anz : L.ST(0) + q2, q2s = c8 ? 0 : L.SS;
+        // (C0, C1 depend on mode)
+        if (t == 0) {
+            st(ac0, C0);
+            st(ac0 + 1, 0);
+            st(ac1, 0);
+            st(ac1 + 1, C1);
+            st(anz, (T)-0.0);
+        }
+        wv.sync();
+        wv.mark(1);
+        // terminal stage
+        T Pij;
+        {
+            const int sb = L.ST(N - 1);
+            Pij = ld(sb + q1);
+            st(a7, 0);
+            st(ao, Pij);
+            if (N >= 2) st(gst, ld(L.ST(N - 2) + gsrc));
+        }
+        bool bad = false;  // a stage's reduced Hessian not positive definite
+        for (int k = N - 2; k >= 0; --k) {
+            const int sb = L.ST(k);
+            // row i of P' and p'_i (16-byte reads of the scratch the previous stage wrote) and all
+            // P-independent stage data, issued together before anything waits on them
+            T pr_[8], g[8], c[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+            wv.sync();
+            ldv<8>(sp + 8 * i, pr_);
+            ldv<8>(gj, g);
+            const T ph = ld(pa);
+            // A_hat column i2: rows 0..5 (rows 6, 7 are zero)
+            ldv<6>(mi, c);
+            const T gnext = ld(L.ST(k > 0 ? k - 1 : 0) + gsrc);  // next stage's G entry
+            T qd6, qd7, cc0j, cc1j;
+            ld2(sb + W_::SQD + 6, qd6, qd7);
+            ld2(cca + ccs * k, cc0j, cc1j);
+            const T qh1 = ld(sb + q1), qh2 = ld(q2a + q2s * k);
+            T hv0j = 0, hv0i = 0;
+            if constexpr (MODEL == 1) {
+                hv0j = ld(hja + hjs * k);
+                hv0i = ld(sb + hvi);
+            }
+            const T tw = model == 1 ? ld(sb + W_::STW) : dt;
+            wv.sched_fence();  // (nothing above consumes a load: no wait here)
+            // M = P' G, entry (i, j) per lane; column 7 adds p' (h = P' d + p')
+            T m0 = ph, m1 = 0;
+#pragma unroll
+            for (int q = 0; q < 8; q += 2) {
+                m0 += pr_[q] * g[q];
+                m1 += pr_[q + 1] * g[q + 1];
+            }
+            wv.sync();  // the previous stage's reads of M are done
+            st(sm + MS * j + i, m0 + m1);
+            wv.sync();
+            // the lane's column of M (all rows), B_hat rows (2,3,5,6,7) of 5, 6 and si
+            T mc[8];
+            ldv<8>(mj, mc);
+            const T m25 = ld(sm + MS * 5 + 2), m55 = ld(sm + MS * 5 + 5), m65 = ld(sm + MS * 5 + 6);
+            const T m26 = ld(sm + MS * 6 + 2), m36 = ld(sm + MS * 6 + 3), m56 = ld(sm + MS * 6 + 5),
+                    m66 = ld(sm + MS * 6 + 6), m76 = ld(sm + MS * 6 + 7);
+            const T mi2 = ld(mi + 2), mi3 = ld(mi + 3), mi5 = ld(mi + 5), mi6 = ld(mi + 6), mi7 = ld(mi + 7);
+
+            // R_tilde = R + B^T P' B, S_tilde = B^T P' A (+ rate coupling) | r_tilde = r + B^T h
+            const T Rt00 = qd6 + (tw * (m25 + m55) + m65);
+            const T Rt01 = tw * (m26 + m56) + m66;
+            const T Rt11 = qd7 + (dt * m36 + m76);
+            const T det = Rt00 * Rt11 - Rt01 * Rt01;
+            bad = bad || !(Rt00 > 0) || !(det > (T)(sizeof(T) == 4 ? 1e-6 : 1e-14) * Rt00 * Rt11);
+            const T rdet = rcp(det);
+            const T i00 = Rt11 * rdet, i01 = -Rt01 * rdet, i11 = Rt00 * rdet;
+            T s0j = tw * (mc[2] + mc[5]) + mc[6] + cc0j;
+            const T s1j = dt * mc[3] + mc[7] + cc1j;
+            T s0i = tw * (mi2 + mi5) + mi6 + cc0i;
+            const T s1i = dt * mi3 + mi7 + cc1i;
+            if constexpr (MODEL == 1) {
+                s0j += hv0j;
+                s0i += hv0i;
+            }
+            // the gains' rows K | kff
+            const T K0 = -(i00 * s0j + i01 * s1j);
+            const T K1 = -(i01 * s0j + i11 * s1j);
+            // (A_hat^T M)(i2, j2) | (A_hat^T h)(i2)
+            T a0 = 0, a1 = 0;
+#pragma unroll
+            for (int q = 0; q < 6; q += 2) {
+                a0 += c[q] * mc[q];
+                a1 += c[q + 1] * mc[q + 1];
+            }
+            const T qh = qh1 + qh2;
+            const T qa = qh + (a0 + a1);
+            Pij = qa + s0i * K0 + s1i * K1;
+            const T P7 = qa + s07 * K0 + s17 * K1;
+            st(a7, P7);
+            st(ao, Pij);
+            wv.sync();  // this stage's reads of M are done
+            if (khbm) {
+                if (gl) gk[WideLayout::KS * k] = i2 == 0 ? K0 : K1;
+            } else {
+                st(ga0 + gak * k, i2 == 0 ? K0 : K1);
+            }
+            st(gst, gnext);
         }
         // a failed inertia test anywhere (the stages after it computed values the retry overwrites)
         if (wv.uni(bad)) {

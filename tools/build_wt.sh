@@ -2,7 +2,8 @@
 # "base", or any name without a variants/<name>/ directory) or a modified copy under
 # variants/<name>/ (diagnostic; not product).  Extra compiler flags for a variant: the
 # environment variable WTF_<name> (e.g. WTF_nolicm="-mllvm -disable-machine-licm";
-# WTF_sep="-DMPCG_FUSE=0": the split solver's separate passes, 1 / 2: one fused sweep alone).
+# WTF_sep="-DMPCG_FUSE=0": the split solver's separate passes, 1 / 2: one fused sweep alone;
+# WTF_ric0="-DMPCG_RIC9=0": the Riccati sweep on the 8x8 lane grid alone).
 # Only the benchmark configuration's instance groups are linked (MPCG_HEADLINE_ONLY:
 # mpcg_wide_inst.hip groups 0 and 1).  Binaries go to exp/ (git-ignored, shipped to the
 # GPU box).
