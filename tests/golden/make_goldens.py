@@ -38,6 +38,15 @@ max_cpu_time 0.5 s as its iteration budget).
                      minutes on 8 cores):
 
     python tests/golden/make_goldens.py option_cases
+
+  general.npz        MPC::Solve's arguments away from the infinity course (any pose, speeds from
+                     reversing to above REF_V, far-off errors and steep polynomials, exact lines and
+                     the all-zero problem) at six shapes (N = 20, 40, 65, 3, the bicycle at N = 25, the
+                     class defaults), seeded; a row is kept when the oracle's status and iteration
+                     count do not depend on its linear algebra.  Not part of "all sets"; the same
+                     bytes on every run:
+
+    python tests/golden/make_goldens.py general
 """
 from __future__ import annotations
 
@@ -211,6 +220,105 @@ def ipopt_features():
     print("budget", budget, "status", np.unique(d["status"], return_counts=True))
     out["keys"] = np.array(params.KEYS)
     np.savez_compressed(os.path.join(HERE, "ipopt_features.npz"), **out)
+
+
+# ---------------------------------------------------------------- general.npz
+# Problems away from the infinity course: MPC::Solve's arguments drawn over their domain instead of
+# produced by the preprocessing of a robot near the lemniscate.  Per category the state ranges and
+# the scale of each polynomial coefficient (uniform in +- the scale):
+#   pose   x, y in [-2, 2], psi in [-1.5, 1.5] (the y row of the initial-state constraint, the
+#          polynomial at x < 0 and |x| > 2)
+#   speed  x = y = psi = 0, v from reversing to above REF_V
+#   far    x = y = psi = 0, cte and epsi far off, steep polynomials (atan of a steep slope, the
+#          objective scaling at a large start gradient)
+#   line   x = y = psi = 0, c0 = cte, c2 = c3 = 0 exactly, c1 = 0 on the even rows and uniform in
+#          +- 0.5 on the odd ones; the first min(8, rows / 2) rows of a shape are the all-zero
+#          problem, the even ones of them with v = REF_V (the start point is the optimum)
+GENERAL_SEED = 2024
+GENERAL_CATEGORIES = {
+    # name: (x, y, psi half-ranges, v range, cte half-range, epsi half-range, coefficient scales)
+    "pose": ((2.0, 2.0, 1.5), (0.0, 0.8), 0.5, 1.0, (0.5, 0.6, 0.2, 0.05)),
+    "speed": ((0.0, 0.0, 0.0), (-0.6, 1.5), 0.3, 0.5, (0.3, 0.4, 0.1, 0.03)),
+    "far": ((0.0, 0.0, 0.0), (0.0, 0.8), 2.5, 3.0, (2.5, 3.0, 1.0, 0.5)),
+    "line": ((0.0, 0.0, 0.0), (0.0, 0.8), 0.4, 0.8, (0.0, 0.5, 0.0, 0.0)),
+}
+GENERAL_SHAPES = {
+    # name: (params, rows per category); BOUND is the parameter set's own
+    "N20": (PLUGIN, 16),
+    "N40": (dict(PLUGIN, STEPS=40), 4),
+    "N65": (dict(PLUGIN, STEPS=65), 2),
+    "bicycle_N25": (BICYCLE, 4),
+    "class_defaults": (params.CLASS_DEFAULTS, 4),
+    "N3": (dict(PLUGIN, STEPS=3), 2),
+}
+GENERAL_MIN_KEPT = 0.95
+
+
+def general_draw(shape, cat):
+    """(state, coeffs) of a shape's rows of a category: a pure function of GENERAL_SEED and the two
+    names' positions in the tables above."""
+    P, n = GENERAL_SHAPES[shape]
+    pose, (v0, v1), cte, eps, scale = GENERAL_CATEGORIES[cat]
+    rng = np.random.default_rng([GENERAL_SEED, list(GENERAL_SHAPES).index(shape), list(GENERAL_CATEGORIES).index(cat)])
+    st = np.zeros((n, 6))
+    st[:, :3] = rng.uniform(-1.0, 1.0, (n, 3)) * np.array(pose)
+    st[:, 3] = rng.uniform(v0, v1, n)
+    st[:, 4] = rng.uniform(-cte, cte, n)
+    st[:, 5] = rng.uniform(-eps, eps, n)
+    cf = rng.uniform(-1.0, 1.0, (n, 4)) * np.array(scale)
+    if cat == "line":
+        cf[:, 0] = st[:, 4]
+        cf[::2, 1] = 0.0
+        nz = min(8, n // 2)
+        st[:nz], cf[:nz] = 0.0, 0.0
+        st[:nz:2, 3] = P["REF_V"]
+    return st + 0.0, cf + 0.0  # (no negative zeros)
+
+
+def write_npz(path, arrays):
+    """np.savez_compressed with fixed member timestamps: the same arrays give the same bytes."""
+    import io
+    import zipfile
+
+    with zipfile.ZipFile(path, "w", zipfile.ZIP_DEFLATED) as zf:
+        for k, v in arrays.items():
+            buf = io.BytesIO()
+            np.lib.format.write_array(buf, np.asanyarray(v), allow_pickle=False)
+            zf.writestr(zipfile.ZipInfo(k + ".npy", date_time=(1980, 1, 1, 0, 0, 0)), buf.getvalue(),
+                        compress_type=zipfile.ZIP_DEFLATED)
+
+
+def general():
+    """tests/golden/general.npz.  A drawn row is kept when the oracle's status and iteration count
+    are the same with the dense solve, the structured solve and one refinement step, and the
+    iteration count is at most MAX_ROW_ITERS; nothing else drops a row (no solver of the project
+    is run here)."""
+    out = {}
+    for shape, (P, n) in GENERAL_SHAPES.items():
+        N = int(P["STEPS"])
+        draws = [general_draw(shape, cat) for cat in GENERAL_CATEGORIES]
+        st, cf = np.concatenate([d[0] for d in draws]), np.concatenate([d[1] for d in draws])
+        cat = np.repeat(np.array(list(GENERAL_CATEGORIES)), n)
+        d = solve_set(P, st, cf)
+        keep = d["iters"] <= MAX_ROW_ITERS
+        for kw in (dict(kkt_structured=1), dict(refine_steps=1)):
+            v = O.mpc_solve_batch(P, st, cf, opts=O.ref_opts(N, **kw), nthreads=os.cpu_count() or 8)
+            keep &= (v["status"] == d["status"]) & (v["iters"] == d["iters"])
+        print(f"general {shape}: kept {keep.sum()} of {len(keep)} ({100.0 * keep.mean():.1f} %), status",
+              np.unique(d["status"][keep], return_counts=True), "iters max", d["iters"][keep].max())
+        if keep.mean() < GENERAL_MIN_KEPT:
+            raise SystemExit(f"general {shape}: fewer than {100 * GENERAL_MIN_KEPT:.0f} % of the rows kept")
+        for c in GENERAL_CATEGORIES:
+            if not keep[cat == c].any():
+                raise SystemExit(f"general {shape}: no row of category {c} kept")
+        for k, v in d.items():
+            out[f"{shape}__{k}"] = v if k == "params" else v[keep]
+        out[f"{shape}__category"] = cat[keep]
+        if "MODEL" in P:
+            out[f"{shape}__model"] = np.int32(P["MODEL"])
+            out[f"{shape}__lf"] = np.float64(P["LF"])
+    out["keys"] = np.array(params.KEYS)
+    write_npz(os.path.join(HERE, "general.npz"), out)
 
 
 def hs071():
@@ -458,6 +566,9 @@ if __name__ == "__main__":
     O.build(force=True)
     if sys.argv[1:2] == ["option_cases"]:  # (not part of "all": a scan of several minutes)
         option_cases()
+        sys.exit(0)
+    if sys.argv[1:2] == ["general"]:  # (not part of "all": it is a pure function of its seed)
+        general()
         sys.exit(0)
     sets = set(sys.argv[1:]) or {"hs071", "preprocess", "infinity", "variants", "bicycle", "features", "cppad"}
     if "hs071" in sets:

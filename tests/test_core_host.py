@@ -205,6 +205,19 @@ def test_wide_core_bicycle_matches_oracle(wide_harness, bicycle_golden):
     compare(r, sub, atol=1e-9)
 
 
+@pytest.mark.parametrize("shape", ["N20", "N40", "N65", "bicycle_N25", "class_defaults", "N3"])
+def test_wide_core_matches_oracle_general(wide_harness, shape):
+    """Problems away from the infinity course (tests/golden/general.npz: any pose with y != 0,
+    speeds from reversing to above REF_V, far-off errors and steep polynomials, exact lines and the
+    all-zero problem): every row of every shape, at every MPCG_HOST_FULL."""
+    from test_solution_host import fixture_set
+
+    P, g = fixture_set("general_" + shape)
+    assert len(g["status"]) >= 8 and set(g["category"]) == {"pose", "speed", "far", "line"}
+    r = run_harness(wide_harness, P, np.ascontiguousarray(g["state"]), np.ascontiguousarray(g["coeffs"]))
+    compare(r, g, atol=1e-9)
+
+
 def _oracle_run(oracle, P, state, coeffs):
     return oracle.mpc_solve_batch(P, state, coeffs, opts=oracle.ref_opts(int(P["STEPS"])), nthreads=4, diag=True)
 

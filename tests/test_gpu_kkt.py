@@ -19,7 +19,7 @@ from test_solution_host import numpy_kkt
 
 pytestmark = pytest.mark.gpu
 
-SHAPES = ["N20", "N40", "N65", "bicycle_N25"]
+SHAPES = ["N20", "N40", "N65", "bicycle_N25", "general_N20", "general_bicycle_N25"]
 _solved = {}
 
 

@@ -31,7 +31,9 @@ SENS_DEVICE_BOUND = min(10 * SENS_DEVICE_MEASURED, 1e-9)
 # headline horizon, the bicycle, an unsplit horizon, the lane loop past stage 63 (N = 65, 80), one
 # problem, and more problems than one CU holds
 SHAPES = {"variants_N3": None, "infinity": slice(0, 24), "bicycle_N25": slice(0, 6), "variants_N40": slice(0, 3),
-          "resto_N65": None, "variants_N80": None, "B1": slice(1, 2), "B130": None}
+          "resto_N65": None, "variants_N80": None, "B1": slice(1, 2), "B130": None,
+          # problems away from the infinity course (tests/golden/general.npz)
+          "general_N20": None, "general_bicycle_N25": None}
 _solved = {}
 
 

@@ -62,16 +62,31 @@ def self_consistent(r, N):
     np.testing.assert_array_equal(x[:, [6 * N, 7 * N - 1]], r["u0"])
 
 
-def against_host(r, h, N):
+def against_host(r, h, N, floor=0.0):
     """the GPU's records r against the host emulation's h; returns the largest multiplier
-    difference, relative to the row's largest multiplier"""
+    difference, relative to the row's largest multiplier (or to floor where that is larger:
+    gradient_floor)"""
     np.testing.assert_array_equal(r["status"], h["status"])
     np.testing.assert_array_equal(r["iters"], h["iters"])
     nx = 8 * N - 2
     assert np.abs(r["sol"][:, :nx] - h["sol"][:, :nx]).max() <= X_ATOL
     mg, mh = r["sol"][:, nx:], h["sol"][:, nx:]  # (z_L | z_U | lambda)
     assert (mg[:, :2 * nx] >= 0).all()
-    return (np.abs(mg - mh).max(axis=1) / np.abs(mh).max(axis=1)).max()
+    return (np.abs(mg - mh).max(axis=1) / np.maximum(np.abs(mh).max(axis=1), floor)).max()
+
+
+def gradient_floor(name, P):
+    """The general sets hold the all-zero problem started at v = REF_V.  Its solution is its start:
+    grad f = 0, no bound is active, so lambda = 0 and z is the barrier's mu / slack, 5e-9.  What the
+    solver returns for lambda there is the rounding of the gradient's two cancelling terms,
+    2 W_V v - 2 W_V REF_V = 200 - 200 (measured: |lambda| <= 1.9e-13 on the host, where the numpy
+    certificate's stationarity residual of the same record is 1.1e-14; two host builds that
+    contract other multiply-adds differ by 7.8e-15 in lambda, 1.5e-6 of the row's 5e-9, and so
+    does an MI355X from the host: 1.546e-6 at N = 20, 1.466e-6 on the bicycle, printed by the
+    test), so the scale a difference is measured against is not below those terms' size on these
+    sets.  With it the sets' figures are 5.9e-16 and 4.0e-16.  Every other row's largest
+    multiplier is above the floor (asserted).  0 for the other shapes: their measure is unchanged."""
+    return 2.0 * P["W_V"] * P["REF_V"] if name.startswith("general_") else 0.0
 
 
 def shape_cases(infinity_golden):
@@ -86,6 +101,9 @@ def shape_cases(infinity_golden):
     cases["bicycle_N25"] = (Pb, gb["state"][:32], gb["coeffs"][:32])
     Pr, gr = fixture_set("resto_N20")
     cases["resto_N20"] = (Pr, gr["state"], gr["coeffs"])
+    for name in ("general_N20", "general_bicycle_N25"):  # (problems away from the infinity course)
+        Pg, gg = fixture_set(name)
+        cases[name] = (Pg, gg["state"], gg["coeffs"])
     return cases
 
 
@@ -103,7 +121,7 @@ def host_records(oracle, infinity_golden, tmp_path_factory):
 
 
 @pytest.mark.parametrize("name,park_capacity", [("N20", 0), ("N40", 0), ("N65", 0), ("bicycle_N25", 0), ("resto_N20", 0),
-                                                ("resto_N20", 1)])
+                                                ("resto_N20", 1), ("general_N20", 0), ("general_bicycle_N25", 0)])
 def test_record_equals_the_host_emulations(torch_cuda, host_records, name, park_capacity):  # noqa: F811
     """N = 20 (split), 40 (unsplit), 65 (two stage blocks), the bicycle at N = 25, and rows that
     enter the restoration phase: written by the parked-problem kernel, and (a park area of one
@@ -118,8 +136,13 @@ def test_record_equals_the_host_emulations(torch_cuda, host_records, name, park_
         d2 = r["diag"][:, 2]  # (1: continued by the parked-problem kernel, 2: solved again after an overflow)
         assert (d2 == 1).all() if park_capacity == 0 else ((d2 == 2).sum() >= len(d2) - 1 and (d2 >= 1).all())
     self_consistent(r, N)
-    d = against_host(r, h, N)
+    floor = gradient_floor(name, h["P"])
+    big = np.abs(h["sol"][:, 8 * N - 2:]).max(axis=1)
+    assert ((big >= floor) | (big < 1e-6)).all()  # (the floor acts on the rows without a multiplier alone)
+    d = against_host(r, h, N, floor)
     print(f"{name} park {park_capacity}: multipliers rel {d:.3e} over {len(r['status'])} rows")
+    if floor:
+        print(f"   (relative to the row's largest multiplier alone: {against_host(r, h, N):.3e})")
     assert d <= MULT_REL_BOUND
 
 

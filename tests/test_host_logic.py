@@ -60,6 +60,31 @@ def test_generator_matches_golden_preprocess():
     np.testing.assert_allclose(cf, z["coeffs"], atol=1e-9, rtol=1e-9)
 
 
+@pytest.mark.parametrize("M", [4, 5, 6, 7, 11, 40, 70])
+def test_off_course_plans_take_their_branches(oracle, M):
+    """tests/off_course.py's robots (the inputs of tests/test_gpu_general.py's preprocessing and
+    tick tests): on the oracle's output every plan takes the branch of the heading rule it is named
+    for, and the vectorised NumPy preprocessing agrees with the oracle on them, with and without
+    delay mode."""
+    import off_course
+
+    assert M in off_course.PLAN_LENGTHS
+    pose, vel, plan, names = off_course.robots(M)
+    seen = set()
+    for delay in (True, False):
+        ref = [oracle.find_best_path(*pose[b], *vel[b], 0.1, plan[b], delay) for b in range(len(pose))]
+        assert all(rc == 0 for rc, _, _ in ref)
+        ost, ocf = np.array([s for _, s, _ in ref]), np.array([c for _, _, c in ref])
+        st, cf = infinity.find_best_path(pose[:, 0], pose[:, 1], pose[:, 2], vel[:, 0], vel[:, 1], vel[:, 2], 0.1, plan,
+                                         delay)
+        np.testing.assert_allclose(cf, ocf, rtol=1e-9, atol=1e-9)
+        np.testing.assert_allclose(st, ost, rtol=1e-9, atol=1e-9)
+        if not delay:
+            seen = off_course.assert_branches(M, pose, plan, names, ost)
+    want = {"no_increment"} if M <= 6 else {"gx_zero", "gy_zero", "wrap", "cutoff", "backwards"}
+    assert seen == want | {"behind", "beside"}
+
+
 @pytest.mark.parametrize("total,world", [(10, 3), (524288, 8), (5, 8), (64, 1)])
 def test_shard_covers_exactly(total, world):
     seen = []

@@ -19,7 +19,9 @@ from test_solution_host import nlp_bounds, numpy_kkt, records, split
 
 # both models, the split / unsplit / two-block horizons, rows through the restoration phase, and a
 # set whose rows mostly end infeasible (the certificate reads any record, not only solutions)
-KKT_SETS = ["infinity", "bicycle_N25", "variants_N40", "variants_N80", "variants_small_bound", "resto_N65"]
+# (general_*: records away from the infinity course -- y != 0, steep polynomials, exact lines)
+KKT_SETS = ["infinity", "bicycle_N25", "variants_N40", "variants_N80", "variants_small_bound", "resto_N65",
+            "general_N20", "general_bicycle_N25"]
 
 
 def host_cert(libmpcg, r, sol=None, rows=None):

@@ -35,7 +35,7 @@ FD_H = 1e-4
 CVT, BRF = 1e-4, 1e-8  # constr_viol_tol, bound_relax_factor of the records' solves (Ipopt's defaults)
 
 DENSE_SETS = {"variants_N3": None, "infinity": range(24), "variants_N40": None, "bicycle_N25": None,
-              "resto_N65": None, "variants_N80": None}
+              "resto_N65": None, "variants_N80": None, "general_N20": None, "general_bicycle_N25": None}
 
 
 def dense_rows(name, r):

@@ -35,11 +35,16 @@ X_ATOL = 1e-7
 # variable at a relaxed bound moves by up to bound_relax_factor max(1, |bound|) while the
 # multipliers stay, and the gradient moves with it -- 2 W_ANGVEL 3e-8 = 6e-6 at ANGVEL = 3, and
 # through the bicycle's v delta / lf term |lambda| dt / lf 1e-8 = 3e-5.
+# The general sets (problems away from the infinity course) are held to the same bound, which stays
+# where the infinity-course rows put it: 2.9e2 on general_N20, 4.144e3 on general_bicycle_N25.
 DUAL_RATIO_MEASURED = 3.151e3
 DUAL_RATIO_BOUND = 10 * DUAL_RATIO_MEASURED
 
 SETS = ["infinity", "variants_class_defaults", "variants_rate_w", "variants_no_rate", "variants_N40", "variants_N3",
-        "variants_small_bound", "variants_N80", "variants_N100", "bicycle_N25", "resto_N20", "resto_N65"]
+        "variants_small_bound", "variants_N80", "variants_N100", "bicycle_N25", "resto_N20", "resto_N65",
+        "general_N20", "general_bicycle_N25"]
+# the shapes of tests/golden/general.npz (fixture_set("general_<shape>"))
+GENERAL_SHAPES = ["N20", "N40", "N65", "bicycle_N25", "class_defaults", "N3"]
 
 
 def fixture_set(name):
@@ -51,6 +56,13 @@ def fixture_set(name):
         g = load_npz("bicycle_N25.npz")
         P = params_from_array(g["params"])
         P.update(MODEL=int(g["model"]), LF=float(g["lf"]))
+        return P, g
+    if name.startswith("general_"):  # tests/golden/general.npz: problems away from the infinity course
+        key = name[len("general_"):]
+        g = {k.split("__", 1)[1]: v for k, v in load_npz("general.npz").items() if k.startswith(key + "__")}
+        P = params_from_array(g["params"])
+        if "model" in g:
+            P.update(MODEL=int(g["model"]), LF=float(g["lf"]))
         return P, g
     fname, key = ("variants.npz", name[len("variants_"):]) if name.startswith("variants_") else ("ipopt_features.npz", name)
     z = load_npz(fname)
@@ -168,6 +180,23 @@ def test_multipliers_satisfy_kkt(rec):
     assert c[:, 2].max() <= o.compl_inf_tol
     # the sharper bound on the unscaling
     assert ratio.max() <= DUAL_RATIO_BOUND
+
+
+def test_general_set_sees_a_dropped_y_row(oracle, tmp_path_factory):
+    """The general set's teeth: the certificate of a `pose` record under the same state with
+    state[1] (y, 0 in every infinity problem) replaced by 0 reports the initial-state row of y as
+    violated by |y0| -- a solver that dropped that row would not pass on this set."""
+    r = records("general_N20", oracle, tmp_path_factory)
+    _, g = fixture_set("general_N20")
+    b = max(np.flatnonzero(g["category"] == "pose"), key=lambda i: abs(r["state"][i, 1]))
+    y0 = r["state"][b, 1]
+    assert abs(y0) >= 0.5 and r["status"][b] == 1
+    assert r["np_cert"][b, 1] <= r["opts"].constr_viol_tol
+    st = r["state"][b].copy()
+    st[1] = 0.0
+    c, _ = numpy_kkt(oracle, r["P"], st, r["coeffs"][b], r["sol"][b])
+    print(f"general_N20 row {b}: y0 = {y0:.4f}, primal violation with y0 dropped {c[1]:.4f}")
+    assert abs(c[1] - abs(y0)) <= 1e-6
 
 
 def test_wrong_unscaling_fails_the_dual_bound(oracle, tmp_path_factory):
