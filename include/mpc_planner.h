@@ -82,6 +82,17 @@ class MPC {
         if (mode == MPCG_START_COLD) _start_rec.clear();
     }
     int last_start_used() const { return _start_used; }
+    // The robot's motion since the last Solve, for the next Solve with start_from_solution on: the
+    // new vehicle frame's origin (dx, dy) and heading dpsi expressed in the last Solve's frame.  The
+    // kept record is shifted by one stage and moved to the new frame (include/mpcg.h
+    // mpcg_shift_solution; a control period equal to DT) before it is used.  One-shot: it applies to
+    // the next Solve only; without it that Solve starts from the record as it is.
+    void carry_motion(double dx, double dy, double dpsi) {
+        _carry[0] = dx;
+        _carry[1] = dy;
+        _carry[2] = dpsi;
+        _have_carry = true;
+    }
     // GPU the solver runs on (default 0); call before the first Solve.
     void set_device(int device) { _device = device; }
 
@@ -106,6 +117,8 @@ class MPC {
     int _start_mode = MPCG_START_COLD, _start_used = MPCG_START_COLD;
     double _start_mu0 = 1e-4;
     vector<double> _start_rec;  // the last Solve's record while start_from_solution is on
+    double _carry[3] = {0, 0, 0};  // carry_motion's argument while _have_carry
+    bool _have_carry = false;
 };
 
 #endif /* MPCG_MPC_PLANNER_H */

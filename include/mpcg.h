@@ -529,8 +529,8 @@ int mpcg_solve_device_sol(mpcg_handle* h, int64_t B, const double* d_state, cons
  * passed the solve, as d_pparams (d_sol aliasing d_start is the exception the solver orders
  * itself).  Results do not depend on the park capacity or the solve order.
  * Refused (-1) before anything is launched: a NULL start or start_mode; precision 1.
- * mpcg_last_kernel reports the k_start_wide instance.  mpcg_multi_*, the ticks and the rollout
- * are unchanged. */
+ * mpcg_last_kernel reports the k_start_wide instance.  mpcg_multi_* and the ticks are unchanged;
+ * the rollout started from each robot's previous record is mpcg_rollout_device_start below. */
 #define MPCG_START_COLD 0
 #define MPCG_START_PRIMAL 1
 #define MPCG_START_FULL 2
@@ -556,6 +556,69 @@ int mpcg_kkt(const mpcg_params* p, int64_t B, const double* state, const double*
              const double* sol, double* cert);
 int mpcg_kkt_device(mpcg_handle* h, int64_t B, const double* d_state, const double* d_coeffs, const double* d_pparams,
                     const double* d_sol, double* d_cert, void* stream);
+
+/* ---- A record carried to the next tick ----
+ * findBestPath poses every problem in the robot's own frame at that tick, so the record of tick t
+ * is, as a start for tick t + 1, one stage late and rotated and translated by the robot's motion.
+ * The shift rule (mpc_ros_amd/csrc/mpcg_shift.h) makes it the start of the next problem; it is by
+ * exactly one stage, so it assumes a control period equal to DT.
+ *   motion [B][3] = (mx, my, mpsi): the new frame's origin and heading, expressed in the old frame.
+ *   With c = cos(mpsi), s = sin(mpsi): a point maps as x' = c (x - mx) + s (y - my), y' =
+ *   -s (x - mx) + c (y - my); a heading as theta' = theta - mpsi (not wrapped: the NLP's theta is a
+ *   free variable); a vector by the rotation alone.
+ * Output record o from source r, N stages:
+ *   states s, k = 0..N-2   o.x[sN + k] = r.x[sN + k + 1], x y theta through the maps; then
+ *                          o.x[sN + 0] = state[s], so the new initial-state rows hold exactly
+ *   controls               o.x[6N + k] = r.x[6N + k + 1] for k = 0..N-3, the last one held
+ *                          (o.x[7N - 2] = r.x[7N - 2]); the same for a
+ *   terminal state         one step of the model from o's stage N-2 under o's control N-2, with
+ *                          the new coeffs and parameter row: the six rows of the last dynamics
+ *                          step have zero defect as mpcg_kkt evaluates them
+ *   zl, zu                 x's index map, no frame map, no stage-0 overwrite; stage N-1 held
+ *   lambda                 o.lambda[sN + k] = r.lambda[sN + k + 1] for k = 0..N-2, the last row
+ *                          held; the (x, y) row pair of every k rotated as a vector
+ * The rule does not validate its input: non-finite entries pass through, and mpcg_solve_start
+ * turns such a start into a cold solve (start_used -1).
+ * state, coeffs, pparams: the NEW problem's (pparams NULL: *p / the handle's parameters).
+ * mask [B] int32 or NULL: where it is 0 the record is copied unchanged.  sol_out may alias sol_in.
+ * mpcg_shift_solution: host arrays, no GPU and no handle.  mpcg_shift_solution_device: device
+ * arrays, one problem per wavefront, queued on `stream`; no allocation, no synchronisation, nothing
+ * traps; capturable.  Host and device agree to rounding (sin / cos). */
+int mpcg_shift_solution(const mpcg_params* p, int64_t B, const double* state, const double* coeffs,
+                        const double* pparams, const double* motion, const int32_t* mask, const double* sol_in,
+                        double* sol_out);
+int mpcg_shift_solution_device(mpcg_handle* h, int64_t B, const double* d_state, const double* d_coeffs,
+                               const double* d_pparams, const double* d_motion, const int32_t* d_mask,
+                               const double* d_sol_in, double* d_sol_out, void* stream);
+/* mpcg_rollout_device with every tick started from the robot's own previous solution.  start_mode:
+ * MPCG_START_COLD or MPCG_START_FULL, the same for all robots (MPCG_START_PRIMAL is refused: a
+ * PRIMAL-started solve inside the rollout's kernel sequence did not repeat bit for bit from call to
+ * call, DESIGN.md "Carry to the next tick"; mpcg_shift_solution_device and mpcg_solve_device_start
+ * compose a PRIMAL tick); mu0: FULL's barrier parameter (read in FULL mode only).  The carry is the caller's, in/out like pose and done (zeros before the first tick):
+ *   carry_sol  [B][mpcg_solution_elems(N)]  the robot's last record
+ *   carry_pose [B][3]                       the pose whose frame that record is in
+ *   carry_ok   [B] int32                    1: the record is a solution (status 1 or 4)
+ *   log_start_used [K][B] int32 or NULL     the mode that ran (mpcg_solve_device_start's start_used)
+ * Per tick, after the preprocessing: robot b uses its record if carry_ok[b] != 0, done[b] == 0 and
+ * start_mode != COLD -- its motion from carry_pose[b] = (X0, Y0, psi0) to the tick's pose (X1, Y1,
+ * psi1) is mx = cos psi0 dX + sin psi0 dY, my = -sin psi0 dX + cos psi0 dY, mpsi = atan2(sin(psi1 -
+ * psi0), cos(psi1 - psi0)), the record is shifted in place and its mode is start_mode; every other
+ * robot runs COLD.  carry_pose[b] takes the tick's pose of a running robot.  The solve is
+ * mpcg_solve_device_start's with start = sol = carry_sol and the robots' parameter rows.  Afterwards
+ * carry_ok[b] = (done[b] == 0 and status[b] is 1 or 4).
+ * K ticks in one call equal K calls of one tick bitwise, the carry included; integrate = 0, K = 1 is
+ * the real robot's warm tick.  With start_mode COLD every log and every state array is bitwise
+ * mpcg_rollout_device's, and the carry holds what mpcg_solve_device_sol would write.
+ * mpcg_last_kernel reports the k_start_wide instance.  Refused (-1) before the first launch:
+ * mpcg_rollout_device's refusals; a NULL carry pointer; PRIMAL or an unknown mode; a mu0 that is not
+ * positive and finite in FULL mode. */
+int mpcg_rollout_device_start(mpcg_handle* h, int64_t B, int32_t K, const double* d_courses,
+                              const int32_t* d_course_len, const int32_t* d_course_of, int32_t C, int32_t Gmax,
+                              int32_t window_wp, int32_t stride, double goal_tol, double max_speed, double min_speed,
+                              int32_t delay_mode, int32_t integrate, double* d_pose, double* d_vel, int32_t* d_cursor,
+                              double* d_ref_v, int32_t* d_done, const mpcg_rollout_logs* logs, void* stream,
+                              int32_t start_mode, double mu0, double* d_carry_sol, double* d_carry_pose,
+                              int32_t* d_carry_ok, int32_t* d_log_start_used);
 
 /* ---- Sensitivities of the solution ----
  * The first-order feedback law around a solution record: gain [B][2][10] (row-major) =

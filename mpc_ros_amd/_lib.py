@@ -123,6 +123,13 @@ SIGNATURES = {
                              C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_double, C.c_int32, C.c_int32,
                              C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(MpcgRolloutLogs),
                              C.c_void_p], C.c_int),
+    "mpcg_rollout_device_start": ([C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
+                                   C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_double, C.c_int32,
+                                   C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                   C.POINTER(MpcgRolloutLogs), C.c_void_p, C.c_int32, C.c_double, C.c_void_p, C.c_void_p,
+                                   C.c_void_p, C.c_void_p], C.c_int),
+    "mpcg_shift_solution": ([_PP, C.c_int64, _dp, _dp, _dp, _dp, _ip, _dp, _dp], C.c_int),
+    "mpcg_shift_solution_device": ([C.c_void_p, C.c_int64] + [C.c_void_p] * 8, C.c_int),
     "mpcg_solve_multi": ([C.c_int, C.POINTER(C.c_int), _PP, C.c_int64, _dp, _dp, _dp, _dp, _ip, _dp, _ip], C.c_int),
     "mpcg_shard_range": ([C.c_int64, C.c_int, C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int64)], C.c_int),
     "mpcg_multi_gather_plan": ([C.c_int64, C.c_int32, C.c_int, C.c_int, C.c_void_p], C.c_int),

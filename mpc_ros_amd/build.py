@@ -13,12 +13,12 @@ ROOT = os.path.dirname(HERE)
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libmpcg.so")
 SOURCES = [os.path.join(CSRC, f) for f in ("mpcg_wide.hip", "mpcg_wide_inst.hip", "mpcg_track.hip", "mpcg_synth.hip",
-                                           "mpcg_kkt.hip", "mpcg_sens.hip",
+                                           "mpcg_kkt.hip", "mpcg_sens.hip", "mpcg_shift.hip",
                                            "mpcg_api.cpp", "mpcg_multi.cpp", "mpc_planner.cpp")]
 INST = os.path.join(CSRC, "mpcg_wide_inst.hip")
 N_INST = 34  # MPCG_INST groups of mpcg_wide_inst.hip (wide_plan.h kWideGroups: the groups of its instance list)
 HEADERS = [os.path.join(CSRC, f) for f in ("ipm_core.h", "wide_core.h", "wide_plan.h", "wave_dev.h", "mpcg_internal.h",
-                                           "mpcg_wide_kern.h", "mpcg_pp.h", "mpcg_window.h", "mpcg_kkt.h", "mpcg_sens.h")] + [
+                                           "mpcg_wide_kern.h", "mpcg_pp.h", "mpcg_window.h", "mpcg_kkt.h", "mpcg_sens.h", "mpcg_shift.h")] + [
     os.path.join(ROOT, "include", f) for f in ("mpcg.h", "mpc_planner.h")]
 ARCH = os.environ.get("MPCG_OFFLOAD_ARCH", "gfx950")
 
@@ -96,6 +96,11 @@ def is_solver_kernel(name: str) -> bool:
     return any(k in name for k in ("k_solve_wide", "k_warm_wide", "k_start_wide", "k_resume_wide"))
 
 
+def is_shift_kernel(name: str) -> bool:
+    """The kernels of mpcg_shift.hip: their scratch and LDS figures are recorded beside the solver's."""
+    return any(k in name for k in ("k_shift_solution", "k_shift_rollout", "k_carry_flag"))
+
+
 def build(force: bool = False, verbose: bool = False, jobs: int | None = None) -> str:
     import shutil
     import tempfile
@@ -152,11 +157,12 @@ def demangle(names):
 
 
 def save_resources(usage: dict, path: str = RESOURCES) -> None:
-    """Register / spill / scratch / occupancy figures of every solver kernel instance and of the
-    restoration phase's out-of-line function, from the build's kernel-resource-usage remarks."""
+    """Register / spill / scratch / occupancy figures of every solver kernel instance, of the
+    restoration phase's out-of-line function and of the shift kernels, from the build's
+    kernel-resource-usage remarks."""
     import json
 
-    keep = {k: v for k, v in usage.items() if is_solver_kernel(k) or "resto_phase" in k}
+    keep = {k: v for k, v in usage.items() if is_solver_kernel(k) or "resto_phase" in k or is_shift_kernel(k)}
     names = demangle(sorted(keep))
     os.makedirs(os.path.dirname(path), exist_ok=True)
     with open(path, "w") as f:

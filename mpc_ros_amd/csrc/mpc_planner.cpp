@@ -133,6 +133,8 @@ vector<double> MPC::SolveRaw(const double* state, const double* coeffs) {
     }
     const int N = _mpc_steps;
     vector<double> traj(3 * (size_t)N);
+    const bool carry = _have_carry;
+    _have_carry = false;  // (one-shot, whatever this Solve does)
     double u0[2] = {0, 0}, obj = 0;
     int32_t status = 0, iters = 0;
     int rc;
@@ -141,6 +143,13 @@ vector<double> MPC::SolveRaw(const double* state, const double* coeffs) {
         const size_t ne = (size_t)mpcg_solution_elems(N);
         int32_t mode = _start_rec.size() == ne ? _start_mode : MPCG_START_COLD, used = 0;
         if (_start_rec.size() != ne) _start_rec.assign(ne, 0.0);
+        if (carry && mode != MPCG_START_COLD) {
+            // (carry_motion: the record to this Solve's frame and stage, in place)
+            const mpcg_params p = effective_params();
+            if (mpcg_shift_solution(&p, 1, state, coeffs, nullptr, _carry, nullptr, _start_rec.data(),
+                                    _start_rec.data()) != 0)
+                mode = MPCG_START_COLD;
+        }
         rc = mpcg_solve_start(_handle, 1, state, coeffs, nullptr, _start_rec.data(), &mode, &_start_mu0, u0,
                               traj.data(), &status, &obj, &iters, nullptr, _start_rec.data(), &used);
         if (_keep_solution) _solution = _start_rec;

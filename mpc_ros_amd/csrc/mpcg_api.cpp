@@ -14,6 +14,7 @@
 #include "mpcg_internal.h"
 #include "mpcg_kkt.h"
 #include "mpcg_sens.h"
+#include "mpcg_shift.h"
 #include "mpcg_pp.h"
 #include "mpcg_window.h"
 
@@ -658,6 +659,54 @@ int mpcg_kkt_device(mpcg_handle* h, int64_t B, const double* d_state, const doub
     return 0;
 }
 
+// ---- the shift rule (mpcg_shift.h) ----
+int mpcg_shift_solution(const mpcg_params* p, int64_t B, const double* state, const double* coeffs,
+                        const double* pparams, const double* motion, const int32_t* mask, const double* sol_in,
+                        double* sol_out) {
+    if (!p) return fail(-1, "null params");
+    if (B < 0) return fail(-1, "negative batch");
+    if (B == 0) return 0;
+    if (!state || !coeffs || !motion || !sol_in || !sol_out)
+        return fail(-1, "state, coeffs, motion, sol_in and sol_out are required");
+    int rc = mpcg_params_check(p);
+    if (rc) return rc;
+    const mpcg::IpmParams P = to_ipm(*p);
+    const mpcg::PPRow row = mpcg::pp_row_pack(P);
+    const int64_t ne = mpcg::shift_record_elems(P.N);
+    std::vector<double> work((size_t)ne);
+    for (int64_t b = 0; b < B; ++b) {
+        const double* in = sol_in + b * ne;
+        double* out = sol_out + b * ne;
+        if (mask && mask[b] == 0) {
+            if (in != out) std::memmove(out, in, sizeof(double) * (size_t)ne);
+            continue;
+        }
+        mpcg::shift_problem(pparams ? pparams + b * MPCG_PP_FIELDS : row.f, P.model, P.N, state + b * 6, coeffs + b * 4,
+                            motion + b * 3, in, out, work.data());
+    }
+    return 0;
+}
+
+int mpcg_shift_solution_device(mpcg_handle* h, int64_t B, const double* d_state, const double* d_coeffs,
+                               const double* d_pparams, const double* d_motion, const int32_t* d_mask,
+                               const double* d_sol_in, double* d_sol_out, void* stream) {
+    int rc = batch_check(h, B);
+    if (rc || B == 0) return rc;
+    if (!d_state || !d_coeffs || !d_motion || !d_sol_in || !d_sol_out)
+        return fail(-1, "state, coeffs, motion, sol_in and sol_out are required");
+    rc = mpcg_params_check(&h->params);
+    if (rc) return rc;
+    if (h->params.steps > 128) return fail(-1, "STEPS must be <= 128");
+    hipError_t e = hipSetDevice(h->device);
+    if (e != hipSuccess) return hip_fail(e, "hipSetDevice");
+    const mpcg::IpmParams P = handle_ipm(h);
+    // (no handle scratch is touched: nothing to order against the handle's other streams)
+    e = mpcg::launch_shift_solution(B, P.N, P.model, mpcg::pp_row_pack(P), d_pparams, d_state, d_coeffs, d_motion, d_mask,
+                                    d_sol_in, d_sol_out, (hipStream_t)stream);
+    if (e != hipSuccess) return hip_fail(e, "shift launch");
+    return 0;
+}
+
 // ---- the feedback gains (mpcg_sens.h) ----
 int mpcg_sens(const mpcg_params* p, int64_t B, const double* state, const double* coeffs, const double* pparams,
               const double* sol, double* gain, double* dx, int32_t* info) {
@@ -809,6 +858,16 @@ int mpcg_preprocess_device(mpcg_handle* h, int64_t B, int32_t M, const double* d
     return mpcg::find_best_path_ws_bytes(B, M) ? with_scratch(h, s, queue) : queue();
 }
 
+// The start of a warm tick (mpcg_rollout_device_start): the caller's carry and what decides its use
+struct WarmTick {
+    int start_mode;         // MPCG_START_*, uniform
+    double mu0;             // FULL's barrier parameter
+    const int32_t* done;    // [B] (after the tick's done mark)
+    double* carry_sol;      // [B][solution_elems(N)] in/out
+    double* carry_pose;     // [B][3] in/out
+    int32_t* carry_ok;      // [B] in/out
+    int32_t* used;          // [B] the mode that ran, or null
+};
 // One tick's inputs and outputs (device pointers)
 static_assert(mpcg::kRowFields == MPCG_PP_FIELDS, "TickLayout's rows are parameter rows");
 struct Tick {
@@ -825,6 +884,7 @@ struct Tick {
     double* traj;          // [B][3][N], or null
     int32_t* status;       // [B], or null
     int32_t* iters;        // [B], or null
+    const WarmTick* warm = nullptr;  // the tick started from the carried records, or null
 };
 
 // Everything a call of ticks allocates, before its first launch: the tick scratch of layout L,
@@ -841,9 +901,26 @@ static int ensure_tick(mpcg_handle* h, const mpcg::TickLayout& L, int64_t B, int
 static int tick(mpcg_handle* h, const Tick& t, const mpcg::TickLayout& L, hipStream_t s) {
     double *st = h->d_tick.at<double>(L.state), *cf = h->d_tick.at<double>(L.coeffs), *u0 = h->d_tick.at<double>(L.u0);
     int rc = queue_preprocess(h, t.B, t.M, t.count, t.pose, t.vel, t.plan, t.delay_mode, st, cf, s);
-    if (rc == 0) rc = queue_solve(h, {t.B, st, cf, t.rows, u0, t.traj, t.status, nullptr, t.iters}, s);
     if (rc) return rc;
-    hipError_t e = mpcg::launch_post(t.B, h->params.dt, h->params.ref_v, t.ref_v, t.vel, u0, t.cmd, s);
+    hipError_t e = hipSuccess;
+    if (const WarmTick* w = t.warm) {
+        // the carried records shifted in place to this tick's frame, then the started solve in
+        // place on them (every robot without a usable record in COLD mode)
+        int32_t *mode = h->d_tick.at<int32_t>(L.mode), *status = t.status ? t.status : h->d_tick.at<int32_t>(L.status);
+        double* mu0 = h->d_tick.at<double>(L.mu0);
+        e = mpcg::launch_shift_rollout(t.B, h->params.steps, h->params.model, w->start_mode, w->mu0, t.rows, st, cf,
+                                       t.pose, w->done, w->carry_ok, w->carry_pose, w->carry_sol, mode, mu0, s);
+        if (e != hipSuccess) return hip_fail(e, "shift launch");
+        rc = queue_solve(h, {t.B, st, cf, t.rows, u0, t.traj, status, nullptr, t.iters, nullptr, w->carry_sol,
+                             {w->carry_sol, mode, mu0, w->used}}, s);
+        if (rc) return rc;
+        e = mpcg::launch_carry_flag(t.B, w->done, status, w->carry_ok, s);
+        if (e != hipSuccess) return hip_fail(e, "carry flag launch");
+    } else {
+        rc = queue_solve(h, {t.B, st, cf, t.rows, u0, t.traj, t.status, nullptr, t.iters}, s);
+        if (rc) return rc;
+    }
+    e = mpcg::launch_post(t.B, h->params.dt, h->params.ref_v, t.ref_v, t.vel, u0, t.cmd, s);
     return e == hipSuccess ? 0 : hip_fail(e, "post-processing launch");
 }
 
@@ -975,11 +1052,13 @@ int mpcg_preprocess_device_n(mpcg_handle* h, int64_t B, int32_t Mmax, const doub
                             (hipStream_t)stream);
 }
 
-int mpcg_rollout_device(mpcg_handle* h, int64_t B, int32_t K, const double* d_courses, const int32_t* d_course_len,
-                        const int32_t* d_course_of, int32_t C, int32_t Gmax, int32_t window_wp, int32_t stride,
-                        double goal_tol, double max_speed, double min_speed, int32_t delay_mode, int32_t integrate,
-                        double* d_pose, double* d_vel, int32_t* d_cursor, double* d_ref_v, int32_t* d_done,
-                        const mpcg_rollout_logs* logs, void* stream) {
+// The rollout, cold (warm null: mpcg_rollout_device) or started from the caller's carry
+// (mpcg_rollout_device_start; log_used [K][B] or null)
+static int rollout(mpcg_handle* h, int64_t B, int32_t K, const double* d_courses, const int32_t* d_course_len,
+                   const int32_t* d_course_of, int32_t C, int32_t Gmax, int32_t window_wp, int32_t stride,
+                   double goal_tol, double max_speed, double min_speed, int32_t delay_mode, int32_t integrate,
+                   double* d_pose, double* d_vel, int32_t* d_cursor, double* d_ref_v, int32_t* d_done,
+                   const mpcg_rollout_logs* logs, void* stream, WarmTick* warm, int32_t* log_used) {
     int rc = batch_check(h, B);
     if (rc) return rc;
     // (every refusal before the first launch: a tick rewrites the robots' state)
@@ -990,20 +1069,32 @@ int mpcg_rollout_device(mpcg_handle* h, int64_t B, int32_t K, const double* d_co
     if (rc) return rc;
     if (!std::isfinite(max_speed) || !std::isfinite(min_speed)) return fail(-1, kSpeedsFinite);
     if (std::isnan(goal_tol)) return fail(-1, "goal_tol must be a number");
+    if (warm) {
+        // (PRIMAL is not offered here: inside the rollout's kernel sequence a PRIMAL-started solve
+        // did not repeat bit for bit from call to call, and K ticks in one call must equal K calls)
+        if (warm->start_mode == MPCG_START_PRIMAL)
+            return fail(-1, "start_mode MPCG_START_PRIMAL is not offered by the rollout: MPCG_START_COLD or _FULL");
+        if (warm->start_mode != MPCG_START_COLD && warm->start_mode != MPCG_START_FULL)
+            return fail(-1, "start_mode must be MPCG_START_COLD or MPCG_START_FULL");
+        if (warm->start_mode == MPCG_START_FULL && !(warm->mu0 > 0 && std::isfinite(warm->mu0)))
+            return fail(-1, "mu0 must be positive and finite in FULL mode");
+    }
     if (B == 0) return 0;
     if (!d_courses || !d_course_len || !d_course_of || !d_pose || !d_vel || !d_cursor || !d_ref_v || !d_done)
         return fail(-1, "courses, course_len, course_of, pose, vel, cursor, ref_v and done are required");
+    if (warm && (!warm->carry_sol || !warm->carry_pose || !warm->carry_ok))
+        return fail(-1, "carry_sol, carry_pose and carry_ok are required");
     hipError_t e = hipSetDevice(h->device);
     if (e != hipSuccess) return hip_fail(e, "hipSetDevice");
     rc = lds_refusal(h);
-    const mpcg::TickLayout L(B, Mmax, 1);
+    const mpcg::TickLayout L(B, Mmax, 1, warm ? 1 : 0);
     if (rc == 0) rc = ensure_tick(h, L, B, 0);
     if (rc) return rc;
     double *rows = h->d_tick.at<double>(L.rows), *cmd = h->d_tick.at<double>(L.cmd), *plan = h->d_tick.at<double>(L.plan);
     int32_t *count = h->d_tick.at<int32_t>(L.count), *start = h->d_tick.at<int32_t>(L.start);
     const mpcg::PPRow row = mpcg::pp_row_pack(to_ipm(h->params));
     const mpcg_rollout_logs lg = logs ? *logs : mpcg_rollout_logs{};
-    Tick t{B, Mmax, d_pose, d_vel, plan, count, delay_mode, rows, d_ref_v, cmd, nullptr, nullptr, nullptr};
+    Tick t{B, Mmax, d_pose, d_vel, plan, count, delay_mode, rows, d_ref_v, cmd, nullptr, nullptr, nullptr, warm};
     mpcg::RolloutArgs a{};  // (what no tick changes: all but the tick's index and its rows of the logs)
     a.B = B;
     a.courses = d_courses;
@@ -1046,6 +1137,7 @@ int mpcg_rollout_device(mpcg_handle* h, int64_t B, int32_t K, const double* d_co
             if (e != hipSuccess) return hip_fail(e, "rollout tick launch");
             t.status = at(lg.status, 1);
             t.iters = at(lg.iters, 1);
+            if (warm) warm->used = at(log_used, 1);
             rc = tick(h, t, L, s);
             if (rc) return rc;
             e = mpcg::launch_rollout_end(a, s);
@@ -1053,6 +1145,29 @@ int mpcg_rollout_device(mpcg_handle* h, int64_t B, int32_t K, const double* d_co
         }
         return 0;
     });
+}
+
+int mpcg_rollout_device(mpcg_handle* h, int64_t B, int32_t K, const double* d_courses, const int32_t* d_course_len,
+                        const int32_t* d_course_of, int32_t C, int32_t Gmax, int32_t window_wp, int32_t stride,
+                        double goal_tol, double max_speed, double min_speed, int32_t delay_mode, int32_t integrate,
+                        double* d_pose, double* d_vel, int32_t* d_cursor, double* d_ref_v, int32_t* d_done,
+                        const mpcg_rollout_logs* logs, void* stream) {
+    return rollout(h, B, K, d_courses, d_course_len, d_course_of, C, Gmax, window_wp, stride, goal_tol, max_speed,
+                   min_speed, delay_mode, integrate, d_pose, d_vel, d_cursor, d_ref_v, d_done, logs, stream, nullptr,
+                   nullptr);
+}
+
+int mpcg_rollout_device_start(mpcg_handle* h, int64_t B, int32_t K, const double* d_courses,
+                              const int32_t* d_course_len, const int32_t* d_course_of, int32_t C, int32_t Gmax,
+                              int32_t window_wp, int32_t stride, double goal_tol, double max_speed, double min_speed,
+                              int32_t delay_mode, int32_t integrate, double* d_pose, double* d_vel, int32_t* d_cursor,
+                              double* d_ref_v, int32_t* d_done, const mpcg_rollout_logs* logs, void* stream,
+                              int32_t start_mode, double mu0, double* d_carry_sol, double* d_carry_pose,
+                              int32_t* d_carry_ok, int32_t* d_log_start_used) {
+    WarmTick w{start_mode, mu0, d_done, d_carry_sol, d_carry_pose, d_carry_ok, nullptr};
+    return rollout(h, B, K, d_courses, d_course_len, d_course_of, C, Gmax, window_wp, stride, goal_tol, max_speed,
+                   min_speed, delay_mode, integrate, d_pose, d_vel, d_cursor, d_ref_v, d_done, logs, stream, &w,
+                   d_log_start_used);
 }
 
 const char* mpcg_last_kernel(const mpcg_handle* h) { return h ? h->last_kernel : ""; }

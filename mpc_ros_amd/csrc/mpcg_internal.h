@@ -74,6 +74,21 @@ hipError_t launch_sens(int64_t B, int N, int model, const PPRow& row, double cvt
                        hipStream_t stream);
 hipError_t launch_sens_apply(int64_t B, const PPRow& row, const double* rows, const double* gain, const double* u0,
                              const double* dstate, const double* dcoeffs, double* u, hipStream_t stream);
+// The shift rule (mpcg_shift.hip, mpcg_shift.h): B records in -> out (may alias) towards the
+// problems (state, coeffs, row / rows) by motion [B][3]; mask [B] (or null) 0: the record copied.
+hipError_t launch_shift_solution(int64_t B, int N, int model, const PPRow& row, const double* rows, const double* state,
+                                 const double* coeffs, const double* motion, const int32_t* mask, const double* in,
+                                 double* out, hipStream_t stream);
+// The warm rollout's two kernels around the solve.  Before it: robot b's carried record shifted in
+// place by the motion from carry_pose[b] to pose[b] where carry_ok[b] != 0, done[b] == 0 and
+// start_mode != COLD (modes[b] = start_mode, else COLD), mu0s[b] = mu0, carry_pose[b] = pose[b]
+// for a running robot.  After it: carry_ok[b] = (done[b] == 0 and status[b] is 1 or 4).
+hipError_t launch_shift_rollout(int64_t B, int N, int model, int start_mode, double mu0, const double* rows,
+                                const double* state, const double* coeffs, const double* pose, const int32_t* done,
+                                const int32_t* carry_ok, double* carry_pose, double* carry_sol, int32_t* modes,
+                                double* mu0s, hipStream_t stream);
+hipError_t launch_carry_flag(int64_t B, const int32_t* done, const int32_t* status, int32_t* carry_ok,
+                             hipStream_t stream);
 // Solve order (expected-longest first): device buffer bytes for B problems, and the
 // launch that writes the workgroup -> problem map into `buf` (returned in *order).
 size_t wide_sched_bytes(int64_t B);

@@ -39,6 +39,30 @@ MPCG_HD KktCert kkt_nan() {
     return KktCert{n, n, n, n};
 }
 
+// One step of the model, F[6] = the stage that follows (sp, up) with zero defect: the right-hand
+// sides of FG_eval's dynamics rows (diff-drive, or model 1 the bicycle), as the rows below subtract
+// them.  Also the terminal stage of a shifted record (mpcg_shift.h).
+MPCG_HD void kkt_step(const double* r, int model, const double* c, const double* sp, const double* up, double* F) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+    const double dt = r[MPCG_PP_DT], lf = r[MPCG_PP_LF];
+    const double x0 = sp[0], y0 = sp[1], th0 = sp[2], v0 = sp[3], eth0 = sp[5];
+    const double turn = model == 1 ? v0 * up[0] / lf * dt : up[0] * dt;
+    double fx = 0.0, pw = 1.0;  // f(x0) = sum c_k x0^k, the powers by repeated multiplication
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        fx += c[q] * pw;
+        pw *= x0;
+    }
+    F[0] = x0 + v0 * cos(th0) * dt;
+    F[1] = y0 + v0 * sin(th0) * dt;
+    F[2] = th0 + turn;
+    F[3] = v0 + up[1] * dt;
+    F[4] = (fx - y0) + v0 * sin(eth0) * dt;
+    F[5] = eth0 + turn;
+}
+
 // One stage.  r: the problem's parameter row (MPCG_PP_*), valid.  c[4], init[6]: the problem.
 // Own values: s[6] u[2] (u read for k < N - 1), zl[8] zu[8] (6 for the last stage), lam[6] the
 // multipliers of the rows into stage k.  Neighbours: sp[6] up[2] of stage k - 1 (read for k >= 1),
@@ -59,20 +83,10 @@ MPCG_HD KktCert kkt_stage(const double* r, int model, int N, int k, const double
 #pragma unroll
         for (int j = 0; j < 6; ++j) g[j] = s[j] - init[j];
     } else {
-        const double x0 = sp[0], y0 = sp[1], th0 = sp[2], v0 = sp[3], eth0 = sp[5];
-        const double turn = model == 1 ? v0 * up[0] / lf * dt : up[0] * dt;
-        double fx = 0.0, pw = 1.0;  // f(x0) = sum c_k x0^k, the powers by repeated multiplication
+        double F[6];
+        kkt_step(r, model, c, sp, up, F);
 #pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            fx += c[q] * pw;
-            pw *= x0;
-        }
-        g[0] = s[0] - (x0 + v0 * cos(th0) * dt);
-        g[1] = s[1] - (y0 + v0 * sin(th0) * dt);
-        g[2] = s[2] - (th0 + turn);
-        g[3] = s[3] - (v0 + up[1] * dt);
-        g[4] = s[4] - ((fx - y0) + v0 * sin(eth0) * dt);
-        g[5] = s[5] - (eth0 + turn);
+        for (int j = 0; j < 6; ++j) g[j] = s[j] - F[j];
     }
 #pragma unroll
     for (int j = 0; j < 6; ++j) o.prim = kkt_max(o.prim, fabs(g[j]));

@@ -390,14 +390,17 @@ struct SolveLayout {
 // state [B][6] | coeffs [B][4] | u0 [B][2] | the robots' parameter rows [B][16] (rows != 0: the
 // tick with a goal, the rollout) | and for the rollout (Mmax > 0: its plan rows per robot) cmd
 // [B][3] | the windows' plans [B][Mmax][2] | count [B] | start [B].  Doubles first, the two int32
-// regions last; every region from an 8-byte boundary.  Nothing in it outlives a call, so the
-// layout may differ from one call to the next.
+// regions last; every region from an 8-byte boundary.  The warm tick (warm != 0: the rollout
+// started from the carried records, mpcg_rollout_device_start) appends mu0 [B] | mode [B] | a status
+// scratch [B] (where the caller logs no status); without it the layout is byte for byte the
+// three-argument one.  Nothing in it outlives a call, so the layout may differ from one call to
+// the next.
 constexpr int kRowFields = 16;  // (MPCG_PP_FIELDS of include/mpcg.h, which this header does not need)
 struct TickLayout {
-    Region state, coeffs, u0, rows, cmd, plan, count, start;
+    Region state, coeffs, u0, rows, cmd, plan, count, start, mu0, mode, status;
     size_t total = 0;
-    TickLayout(int64_t B, int Mmax, int rows_) {
-        const size_t b = (size_t)B, roll = Mmax > 0 ? b : 0;
+    TickLayout(int64_t B, int Mmax, int rows_, int warm = 0) {
+        const size_t b = (size_t)B, roll = Mmax > 0 ? b : 0, wm = warm ? b : 0;
         auto take = [this](size_t bytes) {
             const Region r{total, round_up(bytes, 8)};
             total += r.bytes;
@@ -411,6 +414,9 @@ struct TickLayout {
         plan = take(sizeof(double) * 2 * (size_t)Mmax * roll);
         count = take(sizeof(int32_t) * roll);
         start = take(sizeof(int32_t) * roll);
+        mu0 = take(sizeof(double) * wm);
+        mode = take(sizeof(int32_t) * wm);
+        status = take(sizeof(int32_t) * wm);
     }
 };
 

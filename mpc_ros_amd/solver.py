@@ -150,6 +150,43 @@ def sens_apply(params, gain, u0, dstate, dcoeffs=None, params_rows=None, base: s
     return u
 
 
+def shift_solution(params, state, coeffs, motion, sol, mask=None, params_rows=None, out=None, base: str = "plugin",
+                   **ipopt) -> np.ndarray:
+    """The records sol [B, solution_elems(N)] carried to the next tick on the host (mpcg_shift_solution:
+    no GPU, no handle): shifted by one stage and moved to the frame motion [B, 3] = (mx, my, mpsi) --
+    the new frame's origin and heading in the old frame -- towards the new problems state [B, 6],
+    coeffs [B, 4] (params_rows [B, 16]: their parameter rows).  mask [B] int32: 0 copies the record
+    unchanged.  out: the array written (it may be sol itself); a new one by default.  params: a
+    parameter map or an mpcg_params struct."""
+    p = params if isinstance(params, _lib.MpcgParams) else _params_struct(params, "fp64", ipopt, base)
+    state = np.ascontiguousarray(state, dtype=np.float64)
+    coeffs = np.ascontiguousarray(coeffs, dtype=np.float64)
+    motion = np.ascontiguousarray(motion, dtype=np.float64)
+    B = state.shape[0]
+    ne = solution_elems(p.steps)
+    if out is not sol:
+        sol = np.ascontiguousarray(sol, dtype=np.float64)
+    assert state.shape == (B, 6) and coeffs.shape == (B, 4) and motion.shape == (B, 3) and sol.shape == (B, ne)
+    assert sol.dtype == np.float64 and sol.flags.c_contiguous
+    if out is None:
+        out = np.empty((B, ne))
+    assert out.shape == (B, ne) and out.dtype == np.float64 and out.flags.c_contiguous
+    dp, ip = C.POINTER(C.c_double), C.POINTER(C.c_int32)
+    rows = m = None
+    if params_rows is not None:
+        rows = np.ascontiguousarray(params_rows, dtype=np.float64)
+        assert rows.shape == (B, _lib.PP_FIELDS), "params_rows [B,16]"
+    if mask is not None:
+        m = np.ascontiguousarray(mask, dtype=np.int32)
+        assert m.shape == (B,)
+    _lib.check(_lib.lib().mpcg_shift_solution(
+        C.byref(p), B, state.ctypes.data_as(dp), coeffs.ctypes.data_as(dp),
+        rows.ctypes.data_as(dp) if rows is not None else None, motion.ctypes.data_as(dp),
+        m.ctypes.data_as(ip) if m is not None else None, sol.ctypes.data_as(dp), out.ctypes.data_as(dp)),
+        "mpcg_shift_solution")
+    return out
+
+
 def _on_device(t, shape, dtype="float64"):
     """t is a contiguous torch tensor of this dtype and shape on a GPU."""
     import torch
@@ -385,6 +422,23 @@ class BatchSolver:
         _lib.check(_lib.lib().mpcg_kkt_device(self._h, B, _ptr(state), _ptr(coeffs), _ptr(pparams), _ptr(sol),
                                               _ptr(cert), _stream_ptr(stream, state)), "mpcg_kkt_device")
 
+    def shift_solution_device(self, state, coeffs, motion, sol_in, sol_out, mask=None, pparams=None, stream=None):
+        """The records sol_in [B, solution_elems(N)] carried to the next tick on the device
+        (mpcg_shift_solution_device; the rule: shift_solution): motion [B, 3] float64, mask [B] int32
+        or None, the new problems' state, coeffs and pparams [B, 16] (None: the handle's parameters);
+        sol_out may be sol_in.  Queued on the stream, no allocation."""
+        B = state.shape[0]
+        ne = solution_elems(self.N)
+        for t, shape in ((state, (B, 6)), (coeffs, (B, 4)), (motion, (B, 3)), (sol_in, (B, ne)), (sol_out, (B, ne))):
+            _on_device(t, shape)
+        if mask is not None:
+            _on_device(mask, (B,), "int32")
+        if pparams is not None:
+            _on_device(pparams, (B, _lib.PP_FIELDS))
+        _lib.check(_lib.lib().mpcg_shift_solution_device(
+            self._h, B, _ptr(state), _ptr(coeffs), _ptr(pparams), _ptr(motion), _ptr(mask), _ptr(sol_in),
+            _ptr(sol_out), _stream_ptr(stream, state)), "mpcg_shift_solution_device")
+
     def sens_device(self, state, coeffs, sol, gain, dx=None, info=None, pparams=None, stream=None):
         """The feedback gains of the records sol [B, solution_elems(N)] on the device
         (mpcg_sens_device): gain [B, 2, 10] float64, dx [B, 10, 8N-2] float64 and info [B] int32
@@ -540,7 +594,8 @@ class BatchSolver:
 
     def rollout(self, K: int, courses, course_len, course_of, window_wp: int, stride: int, pose, vel, cursor, ref_v,
                 done, goal_tol: float = 0.1, max_speed: float = 0.7, min_speed: float = 0.05,
-                delay_mode: bool = True, integrate: bool = True, logs: dict | None = None, stream=None):
+                delay_mode: bool = True, integrate: bool = True, logs: dict | None = None, stream=None,
+                start_mode: int = 0, mu0: float = 1e-4, carry: dict | None = None, log_start_used=None):
         """K control ticks of B robots in one enqueue (mpcg_rollout_device): per tick the plan
         window from the robot's course, deceleration towards the course's last waypoint, the
         preprocessing with the robot's own waypoint count, the solve, the post-processing and,
@@ -548,7 +603,12 @@ class BatchSolver:
         float64 and cursor [B], done [B] int32 are in/out: done[b] is the tick (index + 1) at
         which robot b stopped, at its goal (within goal_tol) or at its course's end.  logs: tensors
         by name as rollout_logs(K, B) makes them.  No host synchronisation; call it once before
-        capturing it in a graph (the handle's buffers grow on first use)."""
+        capturing it in a graph (the handle's buffers grow on first use).
+        carry (rollout_carry(B); in/out like pose): every tick starts from the robot's previous
+        solution (mpcg_rollout_device_start) -- start_mode _lib.START_COLD or START_FULL, the same
+        for all robots (START_PRIMAL is refused), mu0 FULL's barrier parameter, log_start_used [K, B] int32 or None the mode that ran.
+        A robot's record is shifted by one stage and moved to the tick's frame where it is usable
+        (carry "ok", a running robot, a mode other than COLD); the others run cold."""
         B = pose.shape[0]
         Cn, Gmax = self._courses(courses, course_len, course_of, B)
         for t, shape, dt in ((pose, (B, 3), "float64"), (vel, (B, 3), "float64"), (ref_v, (B,), "float64"),
@@ -559,11 +619,36 @@ class BatchSolver:
             _on_device(t, *self._log_spec(n, K, B))
             setattr(lg, n, t.data_ptr())
         ptr = _ptr
+        if carry is not None:
+            _on_device(carry["sol"], (B, solution_elems(self.N)))
+            _on_device(carry["pose"], (B, 3))
+            _on_device(carry["ok"], (B,), "int32")
+            if log_start_used is not None:
+                _on_device(log_start_used, (K, B), "int32")
+            _lib.check(_lib.lib().mpcg_rollout_device_start(
+                self._h, B, int(K), ptr(courses), ptr(course_len), ptr(course_of), Cn, Gmax, int(window_wp),
+                int(stride), float(goal_tol), float(max_speed), float(min_speed), int(bool(delay_mode)),
+                int(bool(integrate)), ptr(pose), ptr(vel), ptr(cursor), ptr(ref_v), ptr(done), C.byref(lg),
+                _stream_ptr(stream, pose), int(start_mode), float(mu0), ptr(carry["sol"]), ptr(carry["pose"]),
+                ptr(carry["ok"]), ptr(log_start_used)), "mpcg_rollout_device_start")
+            return
+        if start_mode != 0 or log_start_used is not None:
+            raise ValueError("start_mode and log_start_used need carry")
         _lib.check(_lib.lib().mpcg_rollout_device(
             self._h, B, int(K), ptr(courses), ptr(course_len), ptr(course_of), Cn, Gmax, int(window_wp), int(stride),
             float(goal_tol), float(max_speed), float(min_speed), int(bool(delay_mode)), int(bool(integrate)),
             ptr(pose), ptr(vel), ptr(cursor), ptr(ref_v), ptr(done), C.byref(lg), _stream_ptr(stream, pose)),
             "mpcg_rollout_device")
+
+    def rollout_carry(self, B: int) -> dict:
+        """The carry of rollout(..., carry=), zeroed: "sol" [B, solution_elems(N)] and "pose" [B, 3]
+        float64, "ok" [B] int32."""
+        import torch
+
+        dev = torch.device("cuda", self.device)
+        return dict(sol=torch.zeros((B, solution_elems(self.N)), dtype=torch.float64, device=dev),
+                    pose=torch.zeros((B, 3), dtype=torch.float64, device=dev),
+                    ok=torch.zeros(B, dtype=torch.int32, device=dev))
 
 
 class MultiSolver:
